@@ -20,6 +20,8 @@ How it runs
 Output: the LAST stdout line is one compact JSON object (< 4 KB, compact_line): the contract's keys, `roofline`,
 `cpu_baseline`, `end_to_end`, one small object per leg.  The full record -- per-rank and per-driver detail, counters,
 notes, every plan of an --e2e-sweep -- goes to bench_detail.json next to this script (and to stderr).
+`--dump-outputs DIR` also writes what the headline's last timed step computed as DIR/<name>.npy (dump_outputs), so
+that two builds can be compared output for output: the inputs depend on the arguments alone.
 
 Roofline of the dominant kernel (sw_cont_kernel, integer VALU bound; HIP-event timed on the context's own stream):
 `achieved` = DP cells the kernel really swept (read rows x columns, padding rows and empty quad slots excluded) per
@@ -314,6 +316,12 @@ def rank_main(args):
         elapsed, units_all = float(t.item()), int(u.item())
         dist.barrier()
 
+    dumped = None
+    if getattr(args, "dump_outputs", None) and rank == 0:       # (after the timed region: the last step's results)
+        dumped = dump_outputs(args.dump_outputs, batch.unit_read_off, d_tag.cpu().numpy(), d_h.cpu().numpy(),
+                              d_sc.cpu().numpy(), d_full.cpu().numpy(), d_pref.cpu().numpy(), d_rept.cpu().numpy(),
+                              np.frombuffer(d_calls.cpu().numpy().tobytes(), _lib.CALL_DTYPE))
+
     sw_n, sw_ms = ctx.get_timing(_lib.KERNEL_SW)
     gr_n, gr_ms = ctx.get_timing(_lib.KERNEL_GRID)
     ta_n, ta_ms = ctx.get_timing(_lib.KERNEL_TALLY)
@@ -396,6 +404,8 @@ def rank_main(args):
         }
         if streamed is not None:
             out["streamed"] = streamed
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if n_dev < world:                             # (ranks share devices: a rehearsal or a stub, never a scaling point)
             out["devices"], out["oversubscribed"] = n_dev, True
         if out_dir:
@@ -405,6 +415,37 @@ def rank_main(args):
             print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT = 64 << 20        # --dump-outputs: bytes of all the .npy files together
+DUMP_SEED = 1                # the fixed sample of units when the outputs do not fit
+
+
+def dump_outputs(out_dir, unit_read_off, tag, h, sc, full, pref, rept, calls, limit=DUMP_LIMIT):
+    """--dump-outputs: what genotype_batch handed back in the last timed step, as DIR/<name>.npy.  Every unit's call
+    (calls_<field>.npy, float64: exact for the int32 fields and the f64 likelihoods); the per-read results (tag, h,
+    score) and the histograms (full, pref, rept) as float32 (exact: int16 values, counts < 2^24) for the units of
+    unit_index.npy -- all of them when everything fits in `limit` bytes, else a fixed, seeded sample of units (sorted),
+    their reads in unit order.  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    g = len(calls)
+    uro = np.asarray(unit_read_off, np.int64)
+    arrays = {}
+    for f in calls.dtype.names:
+        if f != "pad":
+            arrays["calls_" + f] = calls[f].astype(np.float64)
+    fixed = sum(a.nbytes for a in arrays.values()) + 16 * 128                    # (+ the .npy headers)
+    per_unit = 3 * full.shape[1] * 4 + np.diff(uro) * 3 * 4 + 8
+    order = np.random.default_rng(DUMP_SEED).permutation(g)
+    k = int(np.searchsorted(np.cumsum(per_unit[order]), limit - fixed, side="right"))
+    units = np.sort(order[:k])
+    reads = np.concatenate([np.arange(uro[u], uro[u + 1]) for u in units]) if k else np.zeros(0, np.int64)
+    arrays["unit_index"] = units.astype(np.float64)
+    arrays.update(tag=tag[reads].astype(np.float32), h=h[reads].astype(np.float32), score=sc[reads].astype(np.float32),
+                  full=full[units].astype(np.float32), pref=pref[units].astype(np.float32), rept=rept[units].astype(np.float32))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def streamed_leg(ctx, torch, dev, batches, args, params, resident_rate):
@@ -883,8 +924,9 @@ def _read_leg(out_dir, drivers):
 
 
 # ---- launcher ------------------------------------------------------------------------------------------------
-def run_ranks(args, n, n_devices):
-    """Start n ranks of this script (rank r on device r mod n_devices) and return (rank 0's line, per-rank records)."""
+def run_ranks(args, n, n_devices, dump=None):
+    """Start n ranks of this script (rank r on device r mod n_devices) and return (rank 0's line, per-rank records).
+    dump: rank 0 writes its last step's outputs there (--dump-outputs)."""
     from tredparse_amd import shard
     argv = [sys.executable, os.path.abspath(__file__), "--gpus", str(n), "--steps", str(args.steps), "--warmup",
             str(args.warmup), "--samples", str(args.samples), "--seed", str(args.seed), "--readlen", str(args.readlen),
@@ -895,6 +937,8 @@ def run_ranks(args, n, n_devices):
         argv += ["--streamed", str(args.streamed)]
     if args.stub:
         argv.append("--stub")
+    if dump:
+        argv += ["--dump-outputs", dump]
     with tempfile.TemporaryDirectory(prefix="tredbench_") as out_dir:
         env = dict(os.environ, TREDBENCH_OUT=out_dir)
         codes = shard.spawn_ranks(argv, n, 0 if args.stub else n_devices, timeout=args.rank_timeout, env=env,
@@ -1047,7 +1091,7 @@ def launcher_main(args):
     # TRED_VIRTUAL_GPUS=V (shard.virtual_gpus): the box's devices counted as V -- the rehearsal of an 8-GPU run on one GPU
     real = 1 if args.stub else shard.real_gpus(n_devices)
     for n in sweep_counts(args.gpus, n_devices, not args.no_sweep):
-        line, ranks = run_ranks(args, n, n_devices)
+        line, ranks = run_ranks(args, n, n_devices, dump=args.dump_outputs if n == args.gpus else None)
         lines[n] = line
         rec = {"n": n, "value": line["value"], "unit": line["unit"], "ms_per_step": line["ms_per_step"],
                "devices": min(n, n_devices), "ranks": [{k: r[k] for k in ("rank", "device", "units", "elapsed_s")}
@@ -1195,6 +1239,9 @@ def main():
     ap.add_argument("--e2e-python-writer", action="store_true",
                     help="end-to-end legs through the Python result dicts and writers instead of the native writer (A/B)")
     ap.add_argument("--e2e-only", action="store_true", help="run the end-to-end legs alone and print one line per leg (tuning)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (rank 0: calls, histograms, per-read results) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed, seeded sample of units beyond that)")
     ap.add_argument("--e2e-child", help=argparse.SUPPRESS)
     ap.add_argument("--e2e-limit", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -1202,6 +1249,8 @@ def main():
     if args.coverage is None:
         args.coverage = WORKLOADS[args.workload]["synth"].get("coverage", 30.0)
     args.coverage_used = args.coverage
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.e2e_child or ("RANK" in os.environ and "WORLD_SIZE" in os.environ):
         # a rank: onto the CPUs of its GPU's NUMA node (TRED_CPUSET from shard.spawn_ranks) before anything touches the
         # GPU or allocates pinned memory

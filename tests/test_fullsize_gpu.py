@@ -43,8 +43,10 @@ def _run(ctx, b, order=None):
 def test_full_size_properties(ctx, loci):
     _model(ctx)
     sel = [l for l in loci if l["name"] not in ("FXTAS", "AR")]
-    # BASELINE configs[2] at full size: 1 000 samples x 30 loci = 30 000 units, ~2.9 M reads (bench.py's batch)
-    b = synth.build_batch(20260101, sel, 1000, synth.SynthParams(coverage=30), workers=32)
+    # BASELINE configs[2] at full size: 1 000 samples x 30 loci = 30 000 units, ~2.9 M reads (bench.py's batch).  Built
+    # in this process (workers=0): the session's context has the GPU open here, and forked workers would inherit it; the
+    # loci are seeded one by one, so the batch is the one a process pool builds
+    b = synth.build_batch(20260101, sel, 1000, synth.SynthParams(coverage=30), workers=0)
     assert b.n_units == 30000 and b.n_reads > 2500000
     ctx.set_ladders(b.ladders)
     r1 = _run(ctx, b)
@@ -95,7 +97,7 @@ def test_full_size_properties(ctx, loci):
 
 def test_all_loci_tags_against_oracle(ctx, loci):
     """Every read of a 32-locus batch through the pruned (non-dump) kernel path vs the oracle."""
-    b = synth.build_batch(77, loci, 6, synth.SynthParams(coverage=30, expanded_max=150, expanded_frac=0.3), workers=8)
+    b = synth.build_batch(77, loci, 6, synth.SynthParams(coverage=30, expanded_max=150, expanded_frac=0.3), workers=0)
     ctx.set_ladders(b.ladders)
     n = b.n_reads
     tag = np.zeros(n, np.uint8); h = np.zeros(n, np.int16); sc = np.zeros(n, np.int16)
@@ -116,7 +118,7 @@ def test_pruned_path_equals_argmax_of_the_unpruned_dump(ctx, loci, scoring):
     by (score, -units), forward strand before reverse complement, must be what the production launch returns --
     ~60 000 reads over all loci incl. tracts longer than a read, without the CPU oracle's cost."""
     sp = synth.SynthParams(coverage=30, expanded_max=150, expanded_frac=0.3)
-    b = synth.build_batch(1234 + scoring[1], loci, 20, sp, workers=8)
+    b = synth.build_batch(1234 + scoring[1], loci, 20, sp, workers=0)
     ctx.set_ladders(b.ladders)
     n = b.n_reads
     params = _lib.SwParams(scoring[0], scoring[1], scoring[2], scoring[3], 9, 0, 150, 0)

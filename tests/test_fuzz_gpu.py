@@ -1,8 +1,9 @@
 """GPU: fixed-seed slices of the randomised parity campaigns (tools/fuzz_*.py) so that every run of the suite
 re-draws them: the long campaigns logged under profiles/ are the same code with more rounds.
 
-  fuzz_parity     pruned production kernel path vs the reference's own compiled ssw.c (oracle/_ref) read by read:
-                  (tag, h, score); plus the per-template dump field by field on adversarial units
+  fuzz_parity     pruned production kernel path vs the reference's own compiled ssw.c (oracle/_ref; without it the C
+                  restatement tests/test_oracle_sw.py pins to the reference) read by read: (tag, h, score); plus the
+                  per-template dump field by field on adversarial units
   fuzz_selfcheck  production launch vs arg-max over the unpruned per-template dump (GPU only, many reads)
   fuzz_hist       adversarial grid inputs vs the numpy oracle: status, enumeration, four terms per pair, CI, PP
   fuzz_grid       SW -> histograms -> grid on random synthetic batches vs the numpy oracle
@@ -15,10 +16,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libssw.so")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref (the compiled reference ssw.c) is not built")
 def test_fuzz_parity_slice():
     import fuzz_parity
     res = fuzz_parity.campaign(rounds=80, seed=20270301)

@@ -49,8 +49,11 @@ def test_ladder_model_matches_reference_golden_pairs(sw_gold):
     assert checked > 5000
 
 
-@pytest.mark.skipif(not po.have_ref(), reason="oracle/_ref (compiled reference) not present")
-def test_oracle_matches_compiled_reference_random():
+RANDOM_SCORINGS = ((2, 2, 3, 1), (1, 4, 6, 1))        # other scorings the ABI accepts
+
+
+def random_pairs():
+    """Random repeat-locus (read, template) pairs, every read against every template."""
     rng = np.random.default_rng(5)
     reads, refs = [], []
     for _ in range(60):
@@ -68,38 +71,71 @@ def test_oracle_matches_compiled_reference_random():
         refs.append(ref)
     pr = [i for i in range(len(reads)) for _ in range(len(refs))]
     pt = [j for _ in range(len(reads)) for j in range(len(refs))]
-    a = po.sw_pairs(reads, refs, pr, pt, threads=8)
-    b = po.ref_sw_pairs(reads, refs, pr, pt, threads=8)
-    assert np.array_equal(a, b)
-    # other scorings the ABI accepts
-    for scoring in ((2, 2, 3, 1), (1, 4, 6, 1)):
-        a = po.sw_pairs(reads[:20], refs[:20], pr[:400], [j % 20 for j in pt[:400]], scoring=scoring)
-        b = po.ref_sw_pairs(reads[:20], refs[:20], pr[:400], [j % 20 for j in pt[:400]], scoring=scoring)
-        assert np.array_equal(a, b), scoring
+    return reads, refs, pr, pt
 
 
-@pytest.mark.skipif(not po.have_ref(), reason="oracle/_ref (compiled reference) not present")
+def random_answers(sw_pairs):
+    """{name: (score, ref_begin, ref_end, read_begin, read_end) per pair} of random_pairs() under the default scoring
+    and a slice of them under RANDOM_SCORINGS, by sw_pairs (po.sw_pairs or po.ref_sw_pairs).  tools/gen_golden.py
+    stores the reference's in tests/golden/sw_random.npz."""
+    reads, refs, pr, pt = random_pairs()
+    out = {"default": sw_pairs(reads, refs, pr, pt, threads=8)}
+    for scoring in RANDOM_SCORINGS:
+        out["scoring_" + "_".join(map(str, scoring))] = sw_pairs(reads[:20], refs[:20], pr[:400], [j % 20 for j in pt[:400]],
+                                                                  scoring=scoring)
+    return out
+
+
+def test_oracle_matches_compiled_reference_random():
+    """The restatement against the compiled reference's answers on random pairs: the stored ones (tests/golden/
+    sw_random.npz), and -- where oracle/_ref is built -- the live ones, which must still be the stored ones."""
+    want = dict(np.load(os.path.join(GOLD, "sw_random.npz")))
+    if po.have_ref():
+        live = random_answers(po.ref_sw_pairs)
+        assert set(live) == set(want) and all(np.array_equal(live[k], want[k]) for k in want)
+    got = random_answers(po.sw_pairs)
+    assert set(got) == set(want) and len(want["default"]) == 3600
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+
+
+# tools/fuzz_parity.py seed 20271201, round 334: a 300-base (CTG)n read with a few errors against the DM1 ladder
+FAULT_READ = ("TGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCCGCTGCTGCT"
+              "GCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTG"
+              "CTGCTGCCGGTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTNCTGCTGCTGCTGCTCCTGCTGCTGCTGCGGG")
+FAULT_LADDER = ("GCCCGGCCTGGCCACCGC", "CTG", "CGGGGGCCCCGAGCCGCC", 100)
+FAULT_OTHER = "GCCCGGCCTGGCCACCGC" + "CTG" * 20 + "CGGGGGCCCCGAGCCGCC"
+
+
+def fault_answers(classify, sw_pairs):
+    """The fault case's answers by classify / sw_pairs (po.ref_classify and po.ref_sw_pairs, or the restatement's):
+    {cls: (tag, h, score) of [other, read, other] under scoring 1/3/2/2, pairs: the read against every template and the
+    neighbour against one, default: (tag, h, score) of the read under the default scoring}.  tools/gen_golden.py stores
+    the reference's in tests/golden/sw_fault.npz."""
+    ls = po.LocusSet([FAULT_LADDER])
+    zero = np.zeros(3, np.int32)
+    return {"cls": classify([FAULT_OTHER, FAULT_READ, FAULT_OTHER], zero, ls, scoring=(1, 3, 2, 2), threads=1),
+            "pairs": sw_pairs([FAULT_READ, FAULT_OTHER], ls.templates, [0] * len(ls.templates) + [1],
+                              list(range(len(ls.templates))) + [38], scoring=(1, 3, 2, 2), threads=1),
+            "default": classify([FAULT_READ], zero[:1], ls, threads=1)}
+
+
 def test_reference_fault_in_its_cigar_pass_is_reported_not_fatal():
     """tools/fuzz_parity.py seed 20271201, round 334: a 300-base (CTG)n read with a few errors against the DM1 ladder under
     scoring 1/3/2/2 makes the reference's banded_sw (ssw.c:549-633) run off its buffers.  The driver reports the pair
     as REF_CRASHED and the read as tag -1, the neighbours are unaffected, and the restatement -- which has no CIGAR
-    pass -- still answers."""
-    read = ("TGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCCGCTGCTGCT"
-            "GCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTG"
-            "CTGCTGCCGGTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTNCTGCTGCTGCTGCTCCTGCTGCTGCTGCGGG")
-    lad = ("GCCCGGCCTGGCCACCGC", "CTG", "CGGGGGCCCCGAGCCGCC", 100)
-    ls = po.LocusSet([lad])
-    other = "GCCCGGCCTGGCCACCGC" + "CTG" * 20 + "CGGGGGCCCCGAGCCGCC"
-    cls = po.ref_classify([other, read, other], np.zeros(3, np.int32), ls, scoring=(1, 3, 2, 2), threads=1)
-    mine = po.classify([other, read, other], np.zeros(3, np.int32), ls, scoring=(1, 3, 2, 2), threads=1)
+    pass -- still answers.  The reference's answers are the stored ones (tests/golden/sw_fault.npz) or, where oracle/_ref
+    is built, its live ones."""
+    ref = fault_answers(po.ref_classify, po.ref_sw_pairs) if po.have_ref() else dict(np.load(os.path.join(GOLD, "sw_fault.npz")))
+    mine = fault_answers(po.classify, po.sw_pairs)
+    cls = ref["cls"]
     if cls[1, 0] >= 0:
         pytest.skip("this build of the reference survives the input")
-    assert cls[1, 0] == -1 and np.array_equal(cls[[0, 2]], mine[[0, 2]]) and mine[1, 0] > 0
-    pairs = po.ref_sw_pairs([read, other], ls.templates, [0] * len(ls.templates) + [1], list(range(len(ls.templates))) + [38],
-                            scoring=(1, 3, 2, 2), threads=1)
-    assert (pairs[:-1, 0] == po.REF_CRASHED).any() and pairs[-1, 0] == 96
+    assert cls[1, 0] == -1 and np.array_equal(cls[[0, 2]], mine["cls"][[0, 2]]) and mine["cls"][1, 0] > 0
+    pairs = ref["pairs"]
+    assert (pairs[:-1, 0] == po.REF_CRASHED).any() and pairs[-1, 0] == 96 and np.array_equal(pairs[-1], mine["pairs"][-1])
     # under the default scoring the same read goes through
-    assert po.ref_classify([read], np.zeros(1, np.int32), ls, threads=1)[0, 0] >= 0
+    assert ref["default"][0, 0] >= 0 and np.array_equal(ref["default"], mine["default"])
 
 
 def test_oracle_classification_matches_reference_golden():

@@ -181,7 +181,7 @@ def test_short_reads_through_the_pruned_path(ctx, loci, readlen):
     found by tools/fuzz_parity.py).  Non-dump path, every read against the reference's own ssw.c."""
     sel = [l for l in loci if l["name"] in ("HD", "SCA3", "DM1", "FRDA", "SCA10")]
     p = synth.SynthParams(coverage=40, readlen=readlen, min_units=1, max_units=30, sub=0.02, nrate=0.01)
-    b = synth.build_batch(900 + readlen, sel, 3, p, workers=4)
+    b = synth.build_batch(900 + readlen, sel, 3, p, workers=0)          # (in-process: this process holds the GPU)
     ctx.set_ladders(b.ladders)
     n = b.n_reads
     tag = np.zeros(n, np.uint8); h = np.zeros(n, np.int16); sc = np.zeros(n, np.int16)
@@ -200,7 +200,7 @@ def test_quads_across_units_any_unit_order(ctx, loci):
     in between); per read the outputs must be identical, and equal to the reference's."""
     sel = [l for l in loci if l["name"] in ("HD", "DM1", "SCA10", "OPMD", "FRDA", "ULD", "BPES")]
     p = synth.SynthParams(coverage=25, readlen=150, min_units=3, max_units=55)
-    b = synth.build_batch(4242, sel, 5, p, workers=4)
+    b = synth.build_batch(4242, sel, 5, p, workers=0)
     reads = [synth.decode(r) for r in b.codes]
     uro = np.asarray(b.unit_read_off, np.int64)
     ctx.set_ladders(b.ladders)

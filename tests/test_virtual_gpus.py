@@ -32,34 +32,35 @@ def test_virtual_devices_map_onto_the_physical_ones():
 
 
 @pytest.mark.gpu
-def test_bench_with_eight_virtual_gpus(tmp_path):
-    """The driver's `bench.py --gpus 8` on this box: eight ranks on the one GPU for the kernel path, and for every device
-    count of the sweep the host-only leg and the planned leg (inflate, walks, selection on the GPU) over 8 files per GPU;
-    the last stdout line parses, stays under 4 KB, every leg's outputs agree, and the whole command stays far below the
-    driver's limit."""
+def test_bench_with_four_virtual_gpus(tmp_path):
+    """The driver's `bench.py --gpus N` rehearsed on this box with the device counted as four: four ranks on the one GPU
+    for the kernel path, and for every device count of the sweep the host-only leg and the planned leg (inflate, walks,
+    selection on the GPU; one driver per device) over 8 files per GPU; the last stdout line parses, stays under 4 KB,
+    every leg's outputs agree, and the whole command stays far below the driver's limit.  At most four children share
+    the GPU at any time, beside this process's own context (the shared boxes allow six processes on a GPU); the
+    launcher's eight-rank fan-out is tests/test_bench_launcher.py's, without a GPU."""
     import time
-    env = dict(os.environ, TRED_VIRTUAL_GPUS="8")
+    env = dict(os.environ, TRED_VIRTUAL_GPUS="4")
     t0 = time.time()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--samples", "40",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--samples", "40",
                         "--e2e-samples", "8", "--e2e-distinct", "8", "--e2e-seconds", "2", "--e2e-repeats", "2", "--e2e-inflate-batch", "4",
-                        "--legs", "", "--no-cpu-baseline", "--e2e-wgs-samples", "0"], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
+                        "--e2e-drivers", "1", "--legs", "", "--no-cpu-baseline", "--e2e-wgs-samples", "0"],
+                       env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
     seconds = time.time() - t0
     assert p.returncode == 0, p.stderr[-3000:]
     last = p.stdout.strip().splitlines()[-1]
     assert len(last) < 4000
     line = json.loads(last)
-    assert line["n_gpus"] == 8 and line["gpus_visible"] == 8 and line["virtual_gpus"]["physical"] >= 1 and line["value"] > 0
+    assert line["n_gpus"] == 4 and line["gpus_visible"] == 4 and line["virtual_gpus"]["physical"] >= 1 and line["value"] > 0
     sweep = {s["n"]: s for s in line["scaling_sweep"]}
-    assert sorted(sweep) == [1, 2, 4, 8] and all(sweep[n].get("oversubscribed") for n in (2, 4, 8) if n > line["virtual_gpus"]["physical"])
+    assert sorted(sweep) == [1, 2, 4] and all(sweep[n].get("oversubscribed") for n in (2, 4) if n > line["virtual_gpus"]["physical"])
     e = line["end_to_end"]
-    assert e["devices"] == 8 and e["files"] == 64 and e["outputs_identical"] is True and e["value"] > 0 and e.get("oversubscribed") is True
+    assert e["devices"] == 4 and e["files"] == 32 and e["outputs_identical"] is True and e["value"] > 0 and e.get("oversubscribed") is True
     assert len(e["repeats"]) == 2
     with open(os.path.join(ROOT, "bench_detail.json")) as fp:
         detail = json.load(fp)
     legs = detail["end_to_end"]["legs"]
     assert [l["role"] for l in legs] == ["host_only_one_driver_per_gpu", "plan", "plan"] and all("error" not in l for l in legs)
-    assert all(l["outputs"] == 64 for l in legs) and all(d["device"] == "0" for l in legs for d in l["per_driver"]) or line["virtual_gpus"]["physical"] > 1
+    assert all(l["outputs"] == 32 for l in legs) and all(d["device"] == "0" for l in legs for d in l["per_driver"]) or line["virtual_gpus"]["physical"] > 1
     assert legs[1]["pinned_MB_per_gpu"] > 0
     assert seconds < 600, seconds
-    with open(os.path.join(ROOT, "gpurun_out", "r06_virtual8.json") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else str(tmp_path / "r06_virtual8.json"), "w") as fp:
-        json.dump({"seconds": round(seconds, 1), "line": line}, fp)

@@ -39,7 +39,7 @@ def campaign(rounds=6, seed=1, max_pairs=20000):
                               expanded_max=int(rng.choice([0, 120, 200])), expanded_frac=0.4)
         sel = [loci[i] for i in rng.permutation(len(loci))[:int(rng.integers(3, 10))]]
         maxinsert = int(rng.choice([60, 150, 300, 400]))
-        b = synth.build_batch(int(rng.integers(1 << 30)), sel, int(rng.integers(1, 4)), p, maxinsert=maxinsert, workers=8)
+        b = synth.build_batch(int(rng.integers(1 << 30)), sel, int(rng.integers(1, 4)), p, maxinsert=maxinsert, workers=0)   # (in this process: it holds the GPU, a forked worker would inherit it)
         units = b.units.copy()
         units["ploidy"] = rng.choice([1, 2], len(units), p=[0.25, 0.75])
         units["fullsearch"] = rng.random(len(units)) < 0.15

@@ -33,7 +33,7 @@ def draw_round(rng, loci, synth, po, samples=(1, 4)):
                           expanded_frac=0.3)
     sel = [l for l in loci if 36 + len(l["repeat"]) * -(-readlen // len(l["repeat"])) <= 511]
     sel = [sel[i] for i in rng.permutation(len(sel))[:int(rng.integers(4, len(sel) + 1))]]
-    b = synth.build_batch(int(rng.integers(1 << 30)), sel, int(rng.integers(samples[0], samples[1])), p, workers=8)
+    b = synth.build_batch(int(rng.integers(1 << 30)), sel, int(rng.integers(samples[0], samples[1])), p, workers=0)   # (in-process: the caller may hold the GPU)
     reads = [synth.decode(r) for r in b.codes]
     uro, ulad = list(b.unit_read_off), list(b.unit_ladder)
     # adversarial units: pure repeats in any phase / strand, exact template windows, chimeras, N runs, junk
@@ -94,7 +94,9 @@ def draw_round(rng, loci, synth, po, samples=(1, 4)):
 
 
 def campaign(rounds=12, seed=1):
-    """Runs the campaign and returns its summary (tests/test_fuzz_gpu.py runs a fixed-seed slice of it)."""
+    """Runs the campaign and returns its summary (tests/test_fuzz_gpu.py runs a fixed-seed slice of it).  The checker is
+    the reference's own compiled ssw.c (oracle/_ref) where it is built, else the C restatement, which
+    tests/test_oracle_sw.py pins to the reference's stored answers (the summary's `checker` says which)."""
     import torch
     if torch.cuda.is_available():
         torch.cuda.init()
@@ -102,6 +104,8 @@ def campaign(rounds=12, seed=1):
     from tredparse_amd import _lib, synth
     loci = synth.load_loci()
     rng = np.random.default_rng(seed)
+    ref = po.have_ref()
+    classify, sw_pairs = (po.ref_classify, po.ref_sw_pairs) if ref else (po.classify, po.sw_pairs)
     ctx = _lib.Context(0)
     n_reads = n_bad = n_pairs = n_bad_pairs = n_ref_faults = 0
     tags = np.zeros(6, np.int64)
@@ -114,8 +118,8 @@ def campaign(rounds=12, seed=1):
         tag = np.zeros(n, np.uint8); h = np.zeros(n, np.int16); sc = np.zeros(n, np.int16)
         ctx.sw_classify(_lib.MEM_HOST, packed, woff, rlen, n, unit_read_off, unit_ladder, len(unit_ladder),
                         _lib.SwParams(scoring[0], scoring[1], scoring[2], scoring[3], 9, int(clip), readlen, 0), tag, h, sc)
-        cls = po.ref_classify(reads, np.repeat(unit_ladder, np.diff(unit_read_off)), po.LocusSet(b.ladders), clip=clip,
-                              scoring=scoring, threads=0)
+        cls = classify(reads, np.repeat(unit_ladder, np.diff(unit_read_off)), po.LocusSet(b.ladders), clip=clip,
+                       scoring=scoring, threads=0)
         # (reads on which the reference's own CIGAR pass faulted -- oracle/ref_driver.c -- carry tag -1: counted, not compared)
         judged = cls[:, 0] >= 0
         n_ref_faults += int((~judged).sum())
@@ -143,7 +147,7 @@ def campaign(rounds=12, seed=1):
                 lad = int(unit_ladder[g0 + np.searchsorted(sub_off, r, side="right") - 1])
                 for j, t in enumerate(range(ls.lad_off[lad], ls.lad_off[lad + 1])):
                     pr.append(r); pt.append(t); where.append((r, j))
-            want = po.ref_sw_pairs(sub_reads, ls.templates, pr, pt, scoring=scoring, threads=0)
+            want = sw_pairs(sub_reads, ls.templates, pr, pt, scoring=scoring, threads=0)
             got = np.array([dump[r, j, :5] for r, j in where], np.int32)
             faulted = want[:, 0] == po.REF_CRASHED
             n_ref_faults += int(faulted.sum())
@@ -164,6 +168,7 @@ def campaign(rounds=12, seed=1):
     ctx.close()
     return {"reads": int(n_reads), "mismatches": int(n_bad), "template_pairs": int(n_pairs),
             "pair_mismatches": int(n_bad_pairs), "reference_faults": int(n_ref_faults), "rounds": rounds, "seed": seed,
+            "checker": "reference ssw.c" if ref else "restatement",
             "tags_none_full_pref_post_rept_hang": [int(x) for x in tags], "seconds": round(time.time() - t0, 1)}
 
 

@@ -10,6 +10,8 @@ The outputs are plain data (inputs + expected outputs); no reference source is s
   grid.npz/json    IntegratedCaller inputs -> ordered [(h1,h2,ml1..ml4)], alleles, lik, PP, CI,
                    P_h1/P_h2/P_h1h2, label from the reference's models.py
   kde.npz          global_lens -> PEMaxLikModel.pdf
+  sw_random.npz    the compiled reference ssw.c's answers to tests/test_oracle_sw.py's random pairs (random_answers)
+  sw_fault.npz     its answers to the (CTG)n read its CIGAR pass faults on (tests/test_oracle_sw.py fault_answers)
 """
 import json
 import logging
@@ -722,12 +724,21 @@ def gen_debug(loci):
                                 "BamParser and IntegratedCaller loggers parsed into fields", "reads": reads, "pairs": pairs}, fp)
 
 
+def gen_sw_ref():
+    """sw_random.npz / sw_fault.npz: the inputs are tests/test_oracle_sw.py's, only the reference's answers are stored."""
+    from tests import test_oracle_sw as t
+    np.savez_compressed(os.path.join(GOLD, "sw_random.npz"), **t.random_answers(po.ref_sw_pairs))
+    np.savez_compressed(os.path.join(GOLD, "sw_fault.npz"), **t.fault_answers(po.ref_classify, po.ref_sw_pairs))
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     loci = synth.load_loci()
     what = sys.argv[1:] or ["sw", "classify", "grid", "e2e"]
     if "sw" in what:
         gen_sw(loci)
+    if "swref" in what:
+        gen_sw_ref()
     if "classify" in what or "grid" in what:
         ref = refshim.load_reference()
         logging.disable(logging.CRITICAL)
