@@ -472,9 +472,19 @@ SYN_SAMPLES = {
 }
 
 
-def syn_sample(name):
+# Long-read samples (the opt-in long-read path, run_many(long_reads=True)): reads of 600 and 1 000 bp, alleles both
+# shorter and longer than a read.  Stored in run_long.json the way the samples above are stored in run_synall.json.
+LONG_SAMPLES = {
+    "synlong600": (20261600, ["HD", "DM1", "ULD", "SCA10"],
+                   dict(coverage=6.0, readlen=600, ins_mean=900.0, ins_sd=60.0, min_units=10, max_units=260), 0.3),
+    "synlong1000": (20261601, ["HD", "FXS"],
+                    dict(coverage=5.0, readlen=1000, ins_mean=1400.0, ins_sd=80.0, min_units=10, max_units=400), 0.3),
+}
+
+
+def syn_sample(name, table=None):
     from tredparse_amd import synth_bam
-    seed, names, kw, alt_rate = SYN_SAMPLES[name]
+    seed, names, kw, alt_rate = (table or SYN_SAMPLES)[name]
     loci = synth_bam.bench_loci() if names is None else [l for l in synth.load_loci() if l["name"] in names]
     kw = dict(kw)
     wgs_like = kw.pop("wgs_like", False)
@@ -491,7 +501,7 @@ def records_digest(recs):
     return h.hexdigest()
 
 
-def gen_synall(loci_unused, only=None):
+def gen_synall(loci_unused, only=None, table=None, fname="run_synall.json", target="synall"):
     """The reference's run() with default flags on synthetic samples with reads at every locus listed: all 30 loci at
     150 bp (BASELINE configs[1] asks for all TRED loci; the reference's two mini-BAMs cover one locus each), ten loci at
     100 bp and at 250 bp (READLEN from the file, other ladder lengths), four loci at 100x with alleles up to 200 repeats
@@ -500,12 +510,13 @@ def gen_synall(loci_unused, only=None):
     from tredparse_amd import synth_bam
     ref = _load_full_reference()
     out = {}
-    path = os.path.join(GOLD, "run_synall.json")
+    table = table or SYN_SAMPLES
+    path = os.path.join(GOLD, fname)
     if only is not None and os.path.exists(path):         # (the other samples' records stay as they are)
         with open(path) as fp:
             out = json.load(fp)["samples"]
-    for name in (SYN_SAMPLES if only is None else only):
-        loci, recs, h_true = syn_sample(name)
+    for name in (table if only is None else only):
+        loci, recs, h_true = syn_sample(name, table)
         cwd = os.getcwd()
         tmp = tempfile.mkdtemp()
         os.chdir(tmp)
@@ -525,11 +536,12 @@ def gen_synall(loci_unused, only=None):
         print(name + ":", len(recs), "records, readLen", calls.get("readLen"), ",", called, "of", len(names), "loci called;",
               sum(int(calls.get(n + ".1") == h[0]) for n, h in zip(names, h_true.tolist())), "short alleles as simulated;",
               "largest grid entries", max(len(calls.get(n + ".P_h1h2") or {}) for n in names))
-        out[name] = {"seed": SYN_SAMPLES[name][0], "records_sha256": records_digest(recs), "loci": names,
+        out[name] = {"seed": table[name][0], "records_sha256": records_digest(recs), "loci": names,
                      "h_true": h_true.tolist(), "tredCalls": calls}
-    with open(os.path.join(GOLD, "run_synall.json"), "w") as fp:
-        json.dump({"generator": "tools/gen_golden.py synall: the reference's tredparse.tred.run() (v0.7.8 via tools/refshim.py) "
-                                "on the synthetic samples of SYN_SAMPLES; `details` entries as [id, tag, h]",
+    with open(path, "w") as fp:
+        json.dump({"generator": "tools/gen_golden.py {}: the reference's tredparse.tred.run() (v0.7.8 via tools/refshim.py) "
+                                "on the synthetic samples of {}; `details` entries as [id, tag, h]".format(
+                                    target, "SYN_SAMPLES" if table is SYN_SAMPLES else "LONG_SAMPLES"),
                    "samples": out}, fp)
 
 
@@ -760,6 +772,8 @@ def main():
         gen_synall(loci)
     if "synwgs" in what:
         gen_synall(loci, only=["synwgs"])
+    if "long" in what:
+        gen_synall(loci, table=LONG_SAMPLES, fname="run_long.json", target="long")
     if "debug" in what:
         gen_debug(loci)
 

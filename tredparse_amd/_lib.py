@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("TREDGPU_LIB") or os.path.join(HERE, "libtredgpu.so") 
 
 MEM_HOST, MEM_DEVICE = 0, 1
 TAG_NONE, TAG_FULL, TAG_PREF, TAG_POST, TAG_REPT, TAG_HANG, TAG_INVALID = 0, 1, 2, 3, 4, 5, 255
+MAX_READ_LEN, MAX_TEMPLATE_LEN = 480, 511                      # include/tredgpu.h
+MAX_LONG_READ_LEN, MAX_LONG_TEMPLATE_LEN = 2048, 4095          # the long-read path (include/tredlong.h)
 TAG_NAMES = {TAG_FULL: "FULL", TAG_PREF: "PREF", TAG_POST: "POST", TAG_REPT: "REPT", TAG_HANG: "HANG"}
 SPAN = 1000
 
@@ -51,6 +53,9 @@ CALL_DTYPE = np.dtype([("status", "<i4"), ("n_pairs", "<i4"), ("h1", "<i4"), ("h
 assert UNIT_DTYPE.itemsize == C.sizeof(UnitParams) == 64
 assert CALL_DTYPE.itemsize == C.sizeof(Call) == 56
 
+# the long-read path's symbols (include/tredlong.h)
+LONG_EXPORTS = ("tredlong_sw_classify", "tredlong_last_error")
+
 # every symbol include/tredgpu.h declares (tests check the .so exports them all)
 EXPORTS = ("tredgpu_create", "tredgpu_destroy", "tredgpu_last_error", "tredgpu_sync", "tredgpu_get_stream",
            "tredgpu_version", "tredgpu_set_ladders", "tredgpu_set_model", "tredgpu_pack_reads",
@@ -81,6 +86,10 @@ def load():
     lib.tredgpu_last_error.argtypes = [vp]
     lib.tredgpu_last_error.restype = C.c_char_p
     lib.tredgpu_sync.argtypes = [vp]
+    lib.tredlong_sw_classify.argtypes = [vp, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                             C.POINTER(C.c_char_p), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, C.c_int32]
+    lib.tredlong_last_error.argtypes = []
+    lib.tredlong_last_error.restype = C.c_char_p
     lib.tredgpu_get_stream.argtypes = [vp]
     lib.tredgpu_get_stream.restype = vp
     lib.tredgpu_version.restype = C.c_char_p
@@ -205,6 +214,8 @@ class Context:
                 device_id, self.lib.tredgpu_last_error(None).decode()))
         self.h = h
         self.n_ladders = 0
+        self.long_reads = False
+        self._long = None      # the long-read path's ladder table: (ladders, is_long[]) -- see set_ladders
 
     def close(self):
         if getattr(self, "h", None):
@@ -229,7 +240,14 @@ class Context:
         return self.lib.tredgpu_get_stream(self.h)
 
     def set_ladders(self, ladders):
-        """ladders: list of (prefix, repeat, suffix, max_units)."""
+        """ladders: list of (prefix, repeat, suffix, max_units).  With the long-read path on (set_long_reads), a ladder
+        whose longest template exceeds MAX_TEMPLATE_LEN (up to MAX_LONG_TEMPLATE_LEN) is registered with the library as a
+        one-letter stand-in, and every read of it goes to the long kernel."""
+        if self.long_reads:
+            return self._set_ladders_long(ladders)
+        self._set_ladders_native(ladders)
+
+    def _set_ladders_native(self, ladders):
         n = len(ladders)
         arr = lambda k: (C.c_char_p * max(n, 1))(*[l[k].encode() for l in ladders])
         mu = np.asarray([l[3] for l in ladders] or [0], np.int32)
@@ -237,6 +255,109 @@ class Context:
                   "tredgpu_set_ladders")
         self.n_ladders = n
         self.ladders = list(ladders)
+
+    # ---- the long-read path (include/tredlong.h) -------------------------------------------------------------
+    def set_long_reads(self, enabled):
+        """Switch the long-read path on or off (off by default).  On: set_ladders accepts ladders up to
+        MAX_LONG_TEMPLATE_LEN columns, and sw_classify, genotype_batch and genotype_batch_joint (host memory) accept reads
+        up to MAX_LONG_READ_LEN bp.  A read longer than MAX_READ_LEN or on a ladder longer than MAX_TEMPLATE_LEN goes to
+        tredlong_sw_classify; every other read goes to the library's calls exactly as with the path off.  Refused
+        while a registered ladder is longer than MAX_TEMPLATE_LEN and the path is switched off."""
+        enabled = bool(enabled)
+        if not enabled and self._long is not None and any(self._long[1]):
+            raise TredGpuError("a registered ladder is longer than {} columns: register shorter ladders before switching "
+                               "the long-read path off".format(MAX_TEMPLATE_LEN))
+        if enabled and not self.long_reads and getattr(self, "ladders", None) is not None:
+            self.long_reads = True
+            self._set_ladders_long(self.ladders)
+        self.long_reads = enabled
+        if not enabled:
+            self._long = None
+
+    @staticmethod
+    def _template_len(l):
+        prefix, repeat, suffix, mu = l
+        return len(prefix) + len(suffix) + len(repeat) * int(mu) if int(mu) > 0 else len(prefix)
+
+    def _set_ladders_long(self, ladders):
+        ladders = [tuple(l) for l in ladders]
+        for i, l in enumerate(ladders):
+            T = self._template_len(l)
+            if T > MAX_LONG_TEMPLATE_LEN:
+                raise TredGpuError("tredgpu_set_ladders failed: ladder {}: longest template {} exceeds "
+                                   "TREDGPU_MAX_LONG_TEMPLATE_LEN={}".format(i, T, MAX_LONG_TEMPLATE_LEN))
+        is_long = np.array([self._template_len(l) > MAX_TEMPLATE_LEN for l in ladders] or [False], bool)[:len(ladders)]
+        # the library's table: a plain one-letter reference stands in for a long ladder (none of its reads reaches it)
+        self._set_ladders_native([("N", "A", "", 0) if lg else l for l, lg in zip(ladders, is_long)])
+        self.ladders = list(ladders)
+        self._long = (list(ladders), is_long)
+
+    def _check_hist_stride(self, hist_stride, ladder_ids):
+        """The library's hist_stride check against the ladders in full (it only knows the stand-ins of long ones)."""
+        for i in sorted(set(int(k) for k in ladder_ids)):
+            mu = int(self._long[0][i][3])
+            if hist_stride <= mu:
+                raise TredGpuError("hist_stride {} must exceed the max_units {} of ladder {}".format(hist_stride, mu, i))
+
+    def _routed_call(self, mem, read_len, n_reads, unit_read_off, unit_ladder, n_units):
+        """Reads of a call that take the long path (None: none, the call is the library's own)."""
+        if not self.long_reads or self._long is None or n_reads == 0:
+            return None
+        if mem != MEM_HOST:
+            if any(self._long[1]):
+                raise TredGpuError("the long-read path takes host-memory calls (MEM_HOST) only")
+            return None
+        rl = np.asarray(read_len)[:n_reads]
+        uro = np.asarray(unit_read_off)[:n_units + 1].astype(np.int64)
+        lad = np.repeat(np.asarray(unit_ladder)[:n_units], np.diff(uro))
+        longest = int(rl.max())
+        if longest > MAX_LONG_READ_LEN:
+            raise TredGpuError("tredgpu_sw_classify failed: read of {} bp exceeds TREDGPU_MAX_LONG_READ_LEN={}".format(
+                longest, MAX_LONG_READ_LEN))
+        if lad.size and (lad.min() < 0 or lad.max() >= len(self._long[1])):
+            return None                                   # (the library refuses the call with its own message)
+        routed = (rl > MAX_READ_LEN) | (self._long[1][lad] if lad.size else False)
+        return np.nonzero(routed)[0] if routed.any() else None
+
+    def _classify_routed(self, routed, packed, read_off, read_len, unit_read_off, unit_ladder, n_units, params, out_tag,
+                         out_h, out_score, out_dump=None, dump_templates=0, n_reads=None):
+        """sw_classify with the routed reads hidden from the library's kernels (length 0) and aligned by the long
+        kernel into the same output arrays."""
+        rl = np.ascontiguousarray(np.asarray(read_len)[:n_reads], np.int32)
+        masked = rl.copy()
+        masked[routed] = 0
+        p = SwParams(params.match, params.mismatch, params.gap_open, params.gap_extend, params.flank, params.clip,
+                     min(int(params.max_read_len), MAX_READ_LEN), params.reserved)
+        self._chk(self.lib.tredgpu_sw_classify(self.h, MEM_HOST, _ptr(packed), _ptr(read_off), _ptr(masked), n_reads,
+                                               _ptr(unit_read_off), _ptr(unit_ladder), n_units, C.byref(p), _ptr(out_tag),
+                                               _ptr(out_h), _ptr(out_score), _ptr(out_dump), dump_templates),
+                  "tredgpu_sw_classify")
+        woff = np.asarray(read_off)
+        pk = np.asarray(packed)
+        sub_off = np.zeros(len(routed) + 1, np.int64)
+        sub_off[1:] = np.cumsum(woff[routed + 1] - woff[routed])
+        sub = np.ascontiguousarray(np.concatenate([pk[woff[r]:woff[r + 1]] for r in routed]), np.uint32)
+        uro = np.asarray(unit_read_off)[:n_units + 1].astype(np.int64)
+        lad = np.ascontiguousarray(np.repeat(np.asarray(unit_ladder)[:n_units], np.diff(uro))[routed], np.int32)
+        ladders = self._long[0]
+        n_l = len(ladders)
+        arr = lambda k: (C.c_char_p * n_l)(*[l[k].encode() for l in ladders])
+        mu = np.asarray([l[3] for l in ladders], np.int32)
+        m = len(routed)
+        tag, h, sc = np.zeros(m, np.uint8), np.zeros(m, np.int16), np.zeros(m, np.int16)
+        dump = np.zeros((m, dump_templates, 6), np.int16) if out_dump is not None else None
+        sub_len = np.ascontiguousarray(rl[routed])      # (held here: _ptr keeps no reference)
+        prefixes, repeats, suffixes = arr(0), arr(1), arr(2)
+        rc = self.lib.tredlong_sw_classify(self.h, n_l, prefixes, repeats, suffixes, _ptr(mu), _ptr(sub), _ptr(sub_off),
+                                               _ptr(sub_len), m, _ptr(lad), C.byref(p),
+                                               _ptr(tag), _ptr(h), _ptr(sc), _ptr(dump), dump_templates if dump is not None else 0)
+        if rc != 0:
+            raise TredGpuError("tredlong_sw_classify failed ({}): {}".format(rc, self.lib.tredlong_last_error().decode()))
+        np.asarray(out_tag)[routed] = tag
+        np.asarray(out_h)[routed] = h
+        np.asarray(out_score)[routed] = sc
+        if out_dump is not None:
+            np.asarray(out_dump).reshape(-1, dump_templates, 6)[routed] = dump
 
     def set_model(self, step_pdf, stutter_w, gc=.68, score=1.0):
         step = np.ascontiguousarray(step_pdf, np.float64)
@@ -247,6 +368,10 @@ class Context:
 
     def sw_classify(self, mem, packed, read_off, read_len, n_reads, unit_read_off, unit_ladder, n_units,
                     params, out_tag, out_h, out_score, out_dump=None, dump_templates=0):
+        routed = self._routed_call(mem, read_len, n_reads, unit_read_off, unit_ladder, n_units)
+        if routed is not None:
+            return self._classify_routed(routed, packed, read_off, read_len, unit_read_off, unit_ladder, n_units, params,
+                                         out_tag, out_h, out_score, out_dump, dump_templates, n_reads=n_reads)
         self._chk(self.lib.tredgpu_sw_classify(self.h, mem, _ptr(packed), _ptr(read_off), _ptr(read_len),
                                                n_reads, _ptr(unit_read_off), _ptr(unit_ladder), n_units,
                                                C.byref(params), _ptr(out_tag), _ptr(out_h), _ptr(out_score),
@@ -282,6 +407,16 @@ class Context:
                        n_units, params, read_pair_id, global_lens, n_global_total, target_lens,
                        n_target_total, out_tag, out_h, out_score, hist_stride, full_cnt, pref_cnt, rept_cnt,
                        calls):
+        routed = self._routed_call(mem, read_len, n_reads, unit_read_off, unit_ladder, n_units)
+        if routed is not None:
+            # the composition tredgpu_genotype_batch makes of its three host-memory calls, with the long path in the first
+            self._check_hist_stride(hist_stride, range(len(self._long[0])))
+            self._classify_routed(routed, packed, read_off, read_len, unit_read_off, unit_ladder, n_units, params, out_tag,
+                                  out_h, out_score, n_reads=n_reads)
+            self.tally(MEM_HOST, out_tag, out_h, n_reads, unit_read_off, n_units, read_pair_id, hist_stride, full_cnt,
+                       pref_cnt, rept_cnt)
+            return self.likelihood_grid(MEM_HOST, units, n_units, hist_stride, full_cnt, pref_cnt, rept_cnt, global_lens,
+                                        n_global_total, target_lens, n_target_total, calls)
         self._chk(self.lib.tredgpu_genotype_batch(self.h, mem, _ptr(packed), _ptr(read_off), _ptr(read_len),
                                                   n_reads, _ptr(unit_read_off), _ptr(unit_ladder), _ptr(units),
                                                   n_units, C.byref(params), _ptr(read_pair_id),
@@ -295,6 +430,19 @@ class Context:
                              hist_stride, rept_cnt, calls, marg, marg_stride, joint_off, joint, joint_n, joint_total):
         """tredgpu_genotype_batch_joint: SW + tagging -> histograms -> grid with marginals and sparse joint, host arrays,
         one wait."""
+        routed = self._routed_call(MEM_HOST, read_len, n_reads, unit_read_off, unit_ladder, n_units)
+        if routed is not None:
+            # SW (the long path included) -> tally -> grid as three host-memory calls
+            self._check_hist_stride(hist_stride, np.asarray(unit_ladder)[:n_units])
+            self._classify_routed(routed, packed, read_off, read_len, unit_read_off, unit_ladder, n_units, params, out_tag,
+                                  out_h, out_score, n_reads=n_reads)
+            full = np.zeros(n_units * hist_stride, np.int32)
+            pref = np.zeros(n_units * hist_stride, np.int32)
+            self.tally(MEM_HOST, out_tag, out_h, n_reads, unit_read_off, n_units, read_pair_id, hist_stride, full, pref,
+                       rept_cnt)
+            return self.likelihood_grid_joint(MEM_HOST, units, n_units, hist_stride, full, pref, rept_cnt, global_lens,
+                                              n_global_total, target_lens, n_target_total, calls, marg, marg_stride,
+                                              joint_off, joint, joint_n, joint_total)
         self._chk(self.lib.tredgpu_genotype_batch_joint(self.h, _ptr(packed), _ptr(read_off), _ptr(read_len), n_reads,
                                                         _ptr(unit_read_off), _ptr(unit_ladder), _ptr(units), n_units,
                                                         C.byref(params), _ptr(read_pair_id), _ptr(global_lens), n_global_total,

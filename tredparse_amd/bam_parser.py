@@ -25,6 +25,8 @@ FLANKMATCH = 9              # bases of flank an alignment must reach to count as
 DNAPE_ELONGATE = 10 * SPAN  # pairs are collected this far on either side of the tract
 MAX_READ_LEN = 480          # longest read the SW kernel holds (include/tredgpu.h)
 MAX_TEMPLATE_LEN = 511      # longest template (prefix + repeat * max_units + suffix)
+MAX_LONG_READ_LEN = 2048    # the same with the long-read path on (scan_sample(long_reads=True))
+MAX_LONG_TEMPLATE_LEN = 4095
 _Y_SKIP = frozenset((1, 4, 6, 7, 10, 11, 13, 16, 18, 19))   # rows of the chrY table that still attract reads
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _SEQ4 = np.frombuffer(b"=ACMGRSVTWYHKDBN", np.uint8)
@@ -63,7 +65,7 @@ class SampleScan(object):
     """
     __slots__ = ("path", "names", "loci", "readlen", "gender", "ydepth", "unit", "depth", "ploidy", "dropped",
                  "packed", "word_off", "read_len", "seq4", "seq4_off", "name_blob", "name_off", "name_id",
-                 "global_lens", "target_lens", "opened", "_text", "device")
+                 "global_lens", "target_lens", "opened", "_text", "device", "long_reads")
 
     def reads_of(self, k):
         u = self.unit[k]
@@ -155,12 +157,16 @@ def walk_need(coffset, host, results, alt_need=None):
     return need
 
 
-def scan_sample(path, repo, names, clip=False, alts=True, readlen=None, want_sex=None, handle=None, pe=None, alt=None):
+def scan_sample(path, repo, names, clip=False, alts=True, readlen=None, want_sex=None, handle=None, pe=None, alt=None,
+                long_reads=False):
     """Read one sample: sex and read length, then depth / reads / pair lengths of every locus in `names`.
     Never raises for a bad file: `opened` is False and nothing else is filled (the reference returns a result
     with only inferredGender / depthY for such a sample).  pe: (results, global pool, target pool) of the pair walks
-    done where the blocks were inflated, alt: those of the walks over the alternative loci (bamio scan)."""
+    done where the blocks were inflated, alt: those of the walks over the alternative loci (bamio scan).  long_reads: the
+    sample goes to an engine with the long-read path on (Engine(long_reads=True)): admit() keeps reads up to
+    MAX_LONG_READ_LEN bp and ladders up to MAX_LONG_TEMPLATE_LEN columns."""
     s = SampleScan()
+    s.long_reads = bool(long_reads)
     s.path, s.names, s.loci = path, list(names), [repo[n] for n in names]
     s.gender, s.ydepth, s.readlen, s.opened = "Unknown", -1, 150, False
     try:
@@ -206,6 +212,9 @@ def admit(s):
     ladder beyond its column limit.  Each costs only its own unit (the reference, too, loses just the failing
     locus, tred.py:245-249); everything else of the sample is genotyped."""
     s.dropped = {}
+    long_reads = getattr(s, "long_reads", False)
+    max_read = MAX_LONG_READ_LEN if long_reads else MAX_READ_LEN
+    max_template = MAX_LONG_TEMPLATE_LEN if long_reads else MAX_TEMPLATE_LEN
     for k, (t, u) in enumerate(zip(s.loci, s.unit)):
         if u["depth_status"] != 0:
             _log.error("Exception on `%s` %s (depth query failed). Set depth=30", s.path, t.name)
@@ -220,10 +229,10 @@ def admit(s):
             why = "a selected read without a sequence (SEQ '*': len(None) in the reference)"
         elif u["pe_status"] != 0:
             why = "a paired read without an alignment end (pair-length extraction)"
-        elif longest > MAX_READ_LEN:
-            why = "a {} bp read: the SW kernel holds reads up to {} bp".format(longest, MAX_READ_LEN)
-        elif len(t.prefix) + t.period * -(-s.readlen // t.period) + len(t.suffix) > MAX_TEMPLATE_LEN:
-            why = "template ladder longer than {} columns".format(MAX_TEMPLATE_LEN)
+        elif longest > max_read:
+            why = "a {} bp read: the SW kernel holds reads up to {} bp".format(longest, max_read)
+        elif len(t.prefix) + t.period * -(-s.readlen // t.period) + len(t.suffix) > max_template:
+            why = "template ladder longer than {} columns".format(max_template)
         if why:
             _log.error("Exception on `%s` %s (%s)", s.path, t.name, why)
             s.dropped[k] = why

@@ -202,8 +202,12 @@ class UnitResult(object):
 
 
 class Engine(object):
-    def __init__(self, device_id=0, ctx=None):
+    def __init__(self, device_id=0, ctx=None, long_reads=False):
+        """long_reads: switch the context's long-read path on (reads up to 2 048 bp, ladders up to 4 095 columns)."""
         self.ctx = ctx or _lib.Context(device_id)
+        self.long_reads = bool(long_reads)
+        if self.long_reads:
+            self.ctx.set_long_reads(True)
         step, w = load_model()
         self.ctx.set_model(step, w)       # gc=.68, score=1.0 (models.py:106)
         self._ladders = None

@@ -85,7 +85,7 @@ def _select_plan(o, f, loci, sites, regions, readlen, sexed, p):
     return out
 
 
-def _scan_planned(arg, plan, out_addr, out_off, status, crc=None, pe=None, alt=None):
+def _scan_planned(arg, plan, out_addr, out_off, status, crc=None, pe=None, alt=None, long_reads=False):
     """Thread: the sample's scan with its planned blocks preloaded from the inflater's output (crc: the decoder's
     checksums of those blocks -- the scan then does not walk the bytes for the BGZF CRC again; pe: the pair walks'
     results from the device, see scan_sample)."""
@@ -95,7 +95,7 @@ def _scan_planned(arg, plan, out_addr, out_off, status, crc=None, pe=None, alt=N
         if status is not None:
             f.preload(out_addr, out_off, status, crc)
         return scan_sample(o["bam"], o["repo"], o["names"], clip=o["clip"], alts=o["alts"], readlen=plan["readlen"], handle=f,
-                           pe=pe, alt=alt)
+                           pe=pe, alt=alt, long_reads=long_reads)
     finally:
         if status is not None:
             hits, misses = f.preload_clear()
@@ -201,9 +201,10 @@ class _InflateFeeder(object):
     inflaters go only after every scan that reads their buffers has ended."""
     SLOTS = 3
 
-    def __init__(self, chunks, ex, device, walk=False, select=False):
+    def __init__(self, chunks, ex, device, walk=False, select=False, long_reads=False):
         import queue
         self.chunks, self.ex, self.device, self.walk, self.select = chunks, ex, device, walk, bool(select and walk)
+        self.long_reads = bool(long_reads)         # the scans' admit() bounds (scan_sample)
         self.on_device = []                            # DeviceChunks handed out and not yet released by the consumer
         # plans and fills have threads of their own: queued behind a chunk's 28 scans in the scan pool they started only
         # when those were done, and the pool then idled through the next chunk's decode
@@ -347,9 +348,9 @@ class _InflateFeeder(object):
             dev = None
             for a, p in zip(chunk, plans):
                 if p is None:
-                    futs.append(self.ex.submit(collect_sample, a))
+                    futs.append(self.ex.submit(collect_sample, a, self.long_reads))
                 elif status is None or p["n"] == 0:
-                    futs.append(self.ex.submit(_scan_planned, a, p, 0, None, None))
+                    futs.append(self.ex.submit(_scan_planned, a, p, 0, None, None, long_reads=self.long_reads))
                 elif walked is not None and p.get("on_device"):
                     # its reads were selected where the blocks are: no scan -- a SampleScan without per-read arrays, which the
                     # genotyping call fills in (engine.genotype_selected), and the inflater stays this chunk's until then
@@ -367,7 +368,7 @@ class _InflateFeeder(object):
                         pe = (res[p["task_first"]:p["task_first"] + len(p["tasks"])], gp, tp)
                         alt = ares[p["alt_first"]:p["alt_first"] + len(p["alt_tasks"])]
                     futs.append(self.ex.submit(_scan_planned, a, p, out_addr, out_off[k:k + p["n"] + 1], status[k:k + p["n"]],
-                                               crc[k:k + p["n"]], pe, alt))
+                                               crc[k:k + p["n"]], pe, alt, long_reads=self.long_reads))
                 handed += 1                                # (that scan closes its own handle)
             self.busy[job["slot"]] = futs + ([dev.release] if dev is not None else [])
             if dev is not None:

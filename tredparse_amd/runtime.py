@@ -52,7 +52,7 @@ def _options(arg):
                 fullsearch=fullsearch, clip=clip, alts=alts, repeatpairs=repeatpairs, log=log)
 
 
-def collect_sample(arg):
-    """Host half of a sample (thread-safe, no GPU): the native scan of its BAM."""
+def collect_sample(arg, long_reads=False):
+    """Host half of a sample (thread-safe, no GPU): the native scan of its BAM (long_reads: see scan_sample)."""
     o = _options(arg)
-    return scan_sample(o["bam"], o["repo"], o["names"], clip=o["clip"], alts=o["alts"])
+    return scan_sample(o["bam"], o["repo"], o["names"], clip=o["clip"], alts=o["alts"], long_reads=long_reads)

@@ -78,6 +78,9 @@ def set_argparse():
     p.add_argument("--tred", action="append", choices=names, default=None, help="locus to call (repeatable); all if omitted")
     p.add_argument("--haploid", action="append", help="contig to treat as haploid (repeatable)")
     p.add_argument("--useclippedreads", action="store_true", help="count clipped reads as evidence")
+    p.add_argument("--long-reads", dest="long_reads", action="store_true",
+                   help="genotype reads up to 2048 bp and template ladders up to 4095 columns (exact long-read kernel) "
+                        "instead of dropping their loci")
     p.add_argument("--noalts", action="store_true", help="skip the alternative loci where repeat reads get mismapped")
     p.add_argument("--norepeatpairs", action="store_true", help="discard pairs whose reads are both repeat-only")
     p.add_argument("--log", choices=("INFO", "DEBUG"), default="INFO", help="log level")
@@ -291,7 +294,7 @@ def _genotype_scans(engine, task_args, scans, TredGpuError):
         the writers find the host's scan there)."""
         again = []
         for si, s, _ in sub:
-            h = collect_sample(task_args[si])
+            h = collect_sample(task_args[si], getattr(engine, "long_reads", False))
             scans[si] = h
             picks[si] = (si, h, [k for k in range(len(h.names)) if k not in h.dropped] if h.opened else [])
             again.append(picks[si])
@@ -447,7 +450,7 @@ def _chunked(task_args, first, batch):
 
 
 def run_many(task_args, engine, pool=None, batch=64, sink=None, threads=1, lazy_details=False, ahead_batches=2,
-             background_sink=False, inflate_device=None, gpu_walk=False, emit=None, gpu_select=False):
+             background_sink=False, inflate_device=None, gpu_walk=False, emit=None, gpu_select=False, long_reads=None):
     """run() over many samples, `batch` samples per GPU batch.  task_args: a list, or any iterable of run() argument
     tuples (taken lazily, a chunk at a time: a cohort need not be known in advance).  BAMs are scanned by `threads` host
     threads (or the executor given as `pool`), up to `ahead_batches` batches ahead of the GPU (with a single batch in
@@ -462,9 +465,15 @@ def run_many(task_args, engine, pool=None, batch=64, sink=None, threads=1, lazy_
     just inflated; only the blocks of the loci's windows and of the alternative loci come back.  gpu_select (with gpu_walk):
     the read selection, the depth and the 2-bit packing happen there as well (include/tredgpu.h section 5) -- no block comes
     back and no host scan runs for a sample the device could serve; any other is scanned as before.
+    long_reads: the scans keep reads up to 2 048 bp and ladders up to 4 095 columns (scan_sample); None (default): as the
+    engine has it (Engine(long_reads=True)).  The engine must have the long-read path on for the scans to ask for it.
     (Measured and removed: the GPU half of a batch on a thread of its own beside the formatting of the previous batch --
     the two halves fight over the interpreter lock, 20.1-20.4 k against 20.5 k genotypes/s with five drivers, 23.2 k against
     27.5 k with six --, and several decode chunks per genotyping batch, 14.7 / 11.0 k against 25 k: docs/history.)"""
+    if long_reads is None:
+        long_reads = getattr(engine, "long_reads", False)
+    elif long_reads and not getattr(engine, "long_reads", False):
+        raise ValueError("run_many(long_reads=True) needs an engine with the long-read path on (Engine(long_reads=True))")
     n_known = len(task_args) if hasattr(task_args, "__len__") else None
     # (with the blocks inflated on a GPU the scan pool is wanted even for one thread: the feeder hands it the samples the
     #  device could not serve -- with gpu_select that is all a scan thread still does)
@@ -481,7 +490,7 @@ def run_many(task_args, engine, pool=None, batch=64, sink=None, threads=1, lazy_
     feeder = None
     if inflate_device is not None and ex is not None:
         try:
-            feeder = _InflateFeeder(chunks, ex, inflate_device, walk=gpu_walk, select=gpu_select)
+            feeder = _InflateFeeder(chunks, ex, inflate_device, walk=gpu_walk, select=gpu_select, long_reads=long_reads)
         except Exception as e:       # no pinned memory, no device ...: the scans inflate for themselves
             logging.getLogger("tredparse_amd").warning("GPU inflate not available (%s): BGZF blocks are inflated on the host", e)
 
@@ -517,7 +526,7 @@ def run_many(task_args, engine, pool=None, batch=64, sink=None, threads=1, lazy_
                     if chunk is None:
                         more = False
                     else:
-                        ahead.append((chunk, [ex.submit(collect_sample, a) for a in chunk]))
+                        ahead.append((chunk, [ex.submit(collect_sample, a, long_reads) for a in chunk]))
                 if not ahead:
                     return
                 chunk, futs = ahead.popleft()
@@ -527,7 +536,7 @@ def run_many(task_args, engine, pool=None, batch=64, sink=None, threads=1, lazy_
                 yield chunk, scans
         else:
             for chunk in chunks:
-                yield chunk, [collect_sample(a) for a in chunk]
+                yield chunk, [collect_sample(a, long_reads) for a in chunk]
 
     def shut_down():
         if feeder is not None:
@@ -862,7 +871,7 @@ def main(args, quiet=False):
             if tasks:
                 from .engine import Engine
                 mark("main")
-                engine = Engine(device)
+                engine = Engine(device, long_reads=True) if args.long_reads else Engine(device)
                 mark("engine")
 
                 # the samples' files are written natively, from the batch's arrays, on threads of their own (Emitter); a
@@ -873,7 +882,7 @@ def main(args, quiet=False):
                     run_many(tasks, engine, batch=max(1, args.batch_samples), threads=max(1, args.cpus), lazy_details=True,
                              inflate_device=device if (args.gpu_inflate and (args.cpus > 1 or (args.gpu_walk and args.gpu_select))) else None,
                              gpu_walk=args.gpu_walk,
-                             gpu_select=args.gpu_select, emit=emit)
+                             gpu_select=args.gpu_select, emit=emit, long_reads=args.long_reads)
                     mark("run_many returned")
                 finally:
                     emit.close()
