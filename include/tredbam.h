@@ -20,8 +20,10 @@ extern "C" {
 
 typedef struct tredbam tredbam;
 
-/* Open a BAM file: reads the header; the .bai next to it (path + ".bai" or with .bam replaced) is loaded on
- * the first region query.  Returns 0, or <0 with the reason in tredbam_last_error(NULL). */
+/* Open a BAM file: reads the header; the index next to it is loaded on the first region query -- the first of
+ * path + ".bai", the path with its extension replaced by ".bai", path + ".csi", the same with ".csi" (a .bai first, unlike
+ * htslib: a file that has one reads as before).  A .csi (CSIv1: bins of any min_shift / depth, no linear index) is
+ * inflated whole at that point.  Returns 0, or <0 with the reason in tredbam_last_error(NULL). */
 int tredbam_open(const char* path, tredbam** out);
 void tredbam_close(tredbam* b);
 /* message of the last failed call on b (b == NULL: of the last failed tredbam_open in this thread) */
@@ -45,7 +47,8 @@ typedef struct tredbam_rec {
     uint8_t mapq, pad;
 } tredbam_rec;
 
-/* Records overlapping [start, end) on reference tid, found through the .bai (bins + linear index) like htslib;
+/* Records overlapping [start, end) on reference tid, found through the index (bins + the .bai's linear index or the
+ * .csi's bin offsets) like htslib;
  * placed-unmapped reads are returned at their mate's position.  tid < 0: all records in file order, at most
  * `limit` of them (limit <= 0: no limit).  *buf points into memory owned by b, valid until the next call on b.
  * Returns the number of records, or <0 on error. */

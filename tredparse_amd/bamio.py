@@ -5,7 +5,10 @@ nor installable here; this module provides the handful of htslib behaviours the 
 
   AlignmentFile(path).fetch()                   all records in file order        (bam_parser.py:384)
   AlignmentFile(path).fetch(chrom, start, end)  records overlapping [start, end) (bam_parser.py:206,226,333),
-                                                found through the .bai (bins + linear index) like htslib;
+                                                found through the index like htslib: <bam>.bai, <stem>.bai,
+                                                <bam>.csi or <stem>.csi, the first that exists (bins + linear
+                                                index of a .bai; bins of any min_shift / depth and their
+                                                loffsets of a .csi);
                                                 placed-unmapped reads (mate-anchored) are returned at their
                                                 mate's position, as htslib does
   .pileup_depth_sum(chrom, start, end)          sum of per-column read counts of pileup(chrom, start, end)
@@ -25,6 +28,7 @@ here -- and the pure-Python `PyAlignmentFile` otherwise (TREDBAM_PURE_PYTHON=1 f
 tests/test_host_frontend.py checks them against each other record for record.
 """
 import ctypes as C
+import gzip
 import os
 import struct
 import zlib
@@ -180,6 +184,238 @@ def _reg2bins(beg, end):
     return bins
 
 
+def _csi_levels(min_shift, depth):
+    """(shift, first bin) of every level l = 0 .. depth of a CSI's binning scheme."""
+    return [(min_shift + 3 * (depth - l), ((1 << 3 * l) - 1) // 7) for l in range(depth + 1)]
+
+
+def _csi_reg2bins(beg, end, min_shift, depth):
+    """The general reg2bins (CSIv1): the bins of every level that overlap [beg, end)."""
+    end = min(end, 1 << (min_shift + 3 * depth)) - 1
+    bins = []
+    for shift, base in _csi_levels(min_shift, depth):
+        bins.extend(range(base + (beg >> shift), base + (end >> shift) + 1))
+    return bins
+
+
+def _csi_min_off(loff, beg, min_shift, depth):
+    """htslib's min_off for a CSI: the loffset of the deepest bin that holds `beg`, else of the nearest bin left of it on
+    that level, else of its parent, and so on up to bin 0."""
+    b = ((1 << 3 * depth) - 1) // 7 + (beg >> min_shift)
+    while True:
+        if b in loff:
+            return loff[b]
+        if b == 0:
+            return 0
+        first = (((b - 1) >> 3) << 3) + 1
+        b = b - 1 if b > first else (b - 1) >> 3
+
+
+def index_paths(path):
+    """The index files looked for next to a BAM, in order: <bam>.bai, <stem>.bai, <bam>.csi, <stem>.csi.  (htslib tries the
+    .csi first; the .bai first keeps a file that has one read exactly as before.)"""
+    stem = os.path.splitext(path)[0]
+    return (path + ".bai", stem + ".bai", path + ".csi", stem + ".csi")
+
+
+def _parse_csi(data):
+    """A .csi file's bytes (BGZF) -> ([(bins, ()) per contig], (min_shift, depth, [bin -> loffset per contig]))."""
+    try:
+        d = gzip.decompress(data)            # (BGZF is a series of gzip members; every member's CRC-32 is checked)
+    except (OSError, EOFError, zlib.error):
+        raise ValueError("bad CSI: not BGZF")
+    if d[:4] != b"CSI\x01":
+        raise ValueError("bad CSI magic")
+    try:
+        min_shift, depth, l_aux = struct.unpack_from("<3i", d, 4)
+        if not (1 <= min_shift <= 32 and 0 <= depth <= 9 and min_shift + 3 * depth <= 62):
+            raise ValueError("bad CSI header")
+        p = 16 + l_aux
+        n_ref = struct.unpack_from("<i", d, p)[0]; p += 4
+        pseudo = ((1 << 3 * (depth + 1)) - 1) // 7 + 1
+        index, loffs = [], []
+        for _ in range(n_ref):
+            n_bin = struct.unpack_from("<i", d, p)[0]; p += 4
+            bins, loff = {}, {}
+            for _ in range(n_bin):
+                b, lo, n_chunk = struct.unpack_from("<IQi", d, p); p += 16
+                chunks = struct.unpack_from("<{}Q".format(2 * n_chunk), d, p); p += 16 * n_chunk
+                if b != pseudo:                       # (the pseudo-bin holds statistics)
+                    bins[b] = [(chunks[2 * k], chunks[2 * k + 1]) for k in range(n_chunk)]
+                    loff[b] = lo
+            index.append((bins, ()))
+            loffs.append(loff)
+    except struct.error:
+        raise ValueError("truncated CSI")
+    return index, (min_shift, depth, loffs)
+
+
+def csi_depth(lengths, min_shift):
+    """The depth samtools gives a CSI: the levels it takes until 1 << min_shift, times 8 per level, reaches the longest
+    contig + 256."""
+    max_len, s, depth = max(list(lengths) or [0]) + 256, 1 << min_shift, 0
+    while max_len > s:
+        s <<= 3
+        depth += 1
+    return depth
+
+
+def _csi_reg2bin(beg, end, min_shift, depth):
+    """The smallest bin of the CSI scheme that holds [beg, end) (numpy arrays; hts_reg2bin)."""
+    end = end - 1
+    out = np.zeros(len(beg), np.int64)
+    done = np.zeros(len(beg), bool)
+    for shift, base in reversed(_csi_levels(min_shift, depth)[1:]):
+        hit = ~done & ((beg >> shift) == (end >> shift))
+        out[hit] = base + (beg[hit] >> shift)
+        done |= hit
+    return out
+
+
+def _bgzf(data, level=6):
+    """`data` as BGZF blocks of at most 0xff00 bytes, and the empty end-of-file block."""
+    out = []
+    for at in list(range(0, len(data), 0xff00)) + [len(data)]:
+        piece = data[at:at + 0xff00] if at < len(data) else b""
+        co = zlib.compressobj(level, zlib.DEFLATED, -15)
+        body = co.compress(piece) + co.flush()
+        out.append(struct.pack("<4BI2BH2BHH", 0x1f, 0x8b, 8, 4, 0, 0, 0xff, 6, 66, 67, 2, len(body) + 25) + body
+                   + struct.pack("<II", zlib.crc32(piece) & 0xffffffff, len(piece)))
+    return b"".join(out)
+
+
+def csi_bytes(lengths, tid, pos, end, vbeg, vend, unmapped, min_shift=14, depth=None):
+    """A CSIv1 index (BGZF-compressed bytes) of the records of a coordinate-sorted BAM given as arrays in file order: contig,
+    position, end for binning (> pos), virtual offsets of the record and behind it, and the unmapped flag.  A bin's chunks
+    are its runs of records that follow each other in the file; its loffset is the virtual offset of the first record that
+    overlaps the bin.  Per contig the pseudo-bin holds (first offset, last offset) and (mapped, unmapped) counts, as htslib
+    writes it; n_no_coor counts the records without a contig.  depth: csi_depth(lengths, min_shift) by default."""
+    tid, pos, end = (np.asarray(x, np.int64) for x in (tid, pos, end))
+    vbeg, vend = np.asarray(vbeg, np.uint64), np.asarray(vend, np.uint64)
+    unmapped = np.asarray(unmapped, bool)
+    if depth is None:
+        depth = csi_depth(lengths, min_shift)
+    levels = _csi_levels(min_shift, depth)
+    pseudo = ((1 << 3 * (depth + 1)) - 1) // 7 + 1
+    out = [b"CSI\x01", struct.pack("<4i", min_shift, depth, 0, len(lengths))]
+    for t in range(len(lengths)):
+        sel = np.nonzero(tid == t)[0]
+        if not len(sel):
+            out.append(struct.pack("<i", 0))
+            continue
+        p, e, vb, ve = pos[sel], end[sel], vbeg[sel], vend[sel]
+        bins = _csi_reg2bin(p, e, min_shift, depth)
+        order = np.argsort(bins, kind="stable")            # by bin, in file order within a bin
+        bs, vbs, ves = bins[order], vb[order], ve[order]
+        cont = np.zeros(len(order), bool)                  # a record that extends the chunk of the one before it
+        cont[1:] = (bs[1:] == bs[:-1]) & (ves[:-1] == vbs[1:])
+        starts = np.nonzero(~cont)[0]
+        ends = np.append(starts[1:], len(order)) - 1
+        uniq, first_of = np.unique(bs, return_index=True)
+        # loffset: the first record whose end lies behind the bin's start (positions are sorted: it overlaps the bin)
+        level = np.searchsorted(np.array([base for _, base in levels]), uniq, side="right") - 1
+        shift = np.array([sh for sh, _ in levels])[level]
+        beg = (uniq - np.array([base for _, base in levels])[level]) << shift
+        first = np.searchsorted(np.maximum.accumulate(e), beg, side="right")
+        loff = vb[first]
+        chunk_bin = bs[starts]
+        out.append(struct.pack("<i", len(uniq) + 1))
+        for k, b in enumerate(uniq.tolist()):
+            lo, hi = np.searchsorted(chunk_bin, b, side="left"), np.searchsorted(chunk_bin, b, side="right")
+            out.append(struct.pack("<IQi", b, int(loff[k]), int(hi - lo)))
+            out.append(np.stack([vbs[starts[lo:hi]], ves[ends[lo:hi]]], axis=1).astype("<u8").tobytes())
+        n_unmapped = int(unmapped[sel].sum())
+        out.append(struct.pack("<IQi4Q", pseudo, 0, 2, int(vb.min()), int(ve.max()), len(sel) - n_unmapped, n_unmapped))
+    out.append(struct.pack("<Q", int((tid < 0).sum())))
+    return _bgzf(b"".join(out))
+
+
+def _record_table(bam):
+    """(contig lengths, and per record in file order: contig, position, end for binning, virtual offsets of the record and
+    behind it, unmapped flag) of a BAM, read a few hundred blocks at a time with the fields gathered by numpy."""
+    f = PyAlignmentFile(bam)
+    lengths, first = list(f.lengths), f._first
+    bg = f.bg
+    cols = {k: [] for k in ("tid", "pos", "end", "vbeg", "vend", "unmapped")}
+    ref_op = np.array(_CIGAR_CONSUMES_REF + (False,) * 7, bool)
+    try:
+        bg.seek(first)
+        coff = (first >> 16) + bg.block_clen                   # the next block to load
+        # pieces of `buf`: (coffset, first byte used, bytes of the block, compressed length); empty blocks are left out
+        tail, pieces = bg.block[first & 0xFFFF:], [(first >> 16, first & 0xFFFF, len(bg.block), bg.block_clen)]
+        more = bg.block_clen > 0
+        while True:
+            data = [tail]
+            while more and len(pieces) < 256:
+                more = bg._load(coff)
+                if more and bg.block:
+                    data.append(bg.block)
+                    pieces.append((coff, 0, len(bg.block), bg.block_clen))
+                coff += bg.block_clen
+            buf = b"".join(data)
+            n, at, offs = len(buf), 0, []
+            while at + 4 <= n:
+                size = int.from_bytes(buf[at:at + 4], "little")
+                if at + 4 + size > n:
+                    break
+                offs.append(at)
+                at += 4 + size
+            if offs:
+                # a position in `buf` -> virtual offset; the end of a piece is the start of the block behind it
+                starts = np.cumsum([0] + [q[2] - q[1] for q in pieces])
+                bco = np.array([q[0] for q in pieces] + [pieces[-1][0] + pieces[-1][3]], np.int64)
+                bfirst = np.array([q[1] for q in pieces] + [0], np.int64)
+
+                def voff(u):
+                    k = np.searchsorted(starts, u, side="right") - 1
+                    return (bco[k] << 16) | (bfirst[k] + u - starts[k])
+                o = np.array(offs, np.int64)
+                u8 = np.frombuffer(buf, np.uint8)
+
+                def u32(x):
+                    return (u8[x].astype(np.int64) | (u8[x + 1].astype(np.int64) << 8) | (u8[x + 2].astype(np.int64) << 16)
+                            | (u8[x + 3].astype(np.int64) << 24))
+                size = u32(o)
+                tid, pos = u32(o + 4).astype(np.int32).astype(np.int64), u32(o + 8).astype(np.int32).astype(np.int64)
+                l_name = u8[o + 12].astype(np.int64)
+                n_cig, flag = u32(o + 16) & 0xFFFF, u32(o + 16) >> 16
+                ref = np.zeros(len(o), np.int64)
+                for k in range(int(n_cig.max())):
+                    has = np.nonzero(n_cig > k)[0]
+                    c = u32(o[has] + 36 + l_name[has] + 4 * k)
+                    ref[has] += np.where(ref_op[c & 15], c >> 4, 0)
+                unm = (flag & 0x4) != 0
+                cols["tid"].append(tid)
+                cols["pos"].append(pos)
+                cols["end"].append(np.where(unm | (ref <= 0), pos + 1, pos + ref))      # (htslib bam_endpos)
+                cols["unmapped"].append(unm)
+                cols["vbeg"].append(voff(o))
+                cols["vend"].append(voff(o + 4 + size))
+            if not more:
+                break
+            # what is left of the last piece(s) starts the next round
+            starts = np.cumsum([0] + [q[2] - q[1] for q in pieces])
+            k = int(np.searchsorted(starts, at, side="right")) - 1
+            tail = buf[at:]
+            pieces = [] if at >= n else [(pieces[k][0], pieces[k][1] + at - int(starts[k])) + pieces[k][2:]] + pieces[k + 1:]
+            if not pieces:
+                pieces = [(coff, 0, 0, 0)]                  # (nothing carried over: a placeholder of no bytes)
+    finally:
+        f.close()
+    return (lengths,) + tuple(np.concatenate(cols[k]) if cols[k] else np.zeros(0, np.int64)
+                              for k in ("tid", "pos", "end", "vbeg", "vend", "unmapped"))
+
+
+def write_csi(bam, out=None, min_shift=14):
+    """Index the existing coordinate-sorted BAM `bam` as CSI with bins of 1 << min_shift bases at the deepest level (depth
+    as samtools chooses it: csi_depth) into `out` (default <bam>.csi).  Returns the path written."""
+    data = csi_bytes(*_record_table(bam), min_shift=min_shift)
+    out = out or bam + ".csi"
+    with open(out, "wb") as fp:
+        fp.write(data)
+    return out
+
+
 class PyAlignmentFile(object):
     def __init__(self, path, mode="rb"):
         if path.endswith(".cram"):
@@ -236,12 +472,16 @@ class PyAlignmentFile(object):
     def _load_index(self):
         if self._index is not None:
             return
-        for cand in (self.path + ".bai", os.path.splitext(self.path)[0] + ".bai"):
+        for cand in index_paths(self.path):
             if os.path.exists(cand):
                 break
         else:
             raise ValueError("no .bai index next to {}".format(self.path))
         data = open(cand, "rb").read()
+        self._csi = None
+        if cand.endswith(".csi"):
+            self._index, self._csi = _parse_csi(data)
+            return
         if data[:4] != b"BAI\x01":
             raise ValueError("bad BAI magic")
         n_ref = struct.unpack_from("<i", data, 4)[0]
@@ -277,9 +517,17 @@ class PyAlignmentFile(object):
             raise ValueError("invalid coordinates: start > end")
         self._load_index()
         bins, lin = self._index[tid]
-        min_off = lin[min(start >> 14, len(lin) - 1)] if lin else 0
+        if self._csi is not None:                     # (a .csi: no linear index, the bins' loffsets instead)
+            min_shift, depth, loffs = self._csi
+            if start >= 1 << (min_shift + 3 * depth):
+                return
+            min_off = _csi_min_off(loffs[tid], start, min_shift, depth)
+            query = _csi_reg2bins(start, max(end, start + 1), min_shift, depth)
+        else:
+            min_off = lin[min(start >> 14, len(lin) - 1)] if lin else 0
+            query = _reg2bins(start, max(end, start + 1))
         chunks = []
-        for b in _reg2bins(start, max(end, start + 1)):
+        for b in query:
             for cb, ce in bins.get(b, ()):
                 if ce > min_off:
                     chunks.append((max(cb, min_off), ce))
@@ -765,7 +1013,7 @@ class NativeAlignmentFile(object):
             raise ValueError("no .bai index next to {}".format(self.path))
 
     def _has_index(self):
-        return any(os.path.exists(c) for c in (self.path + ".bai", os.path.splitext(self.path)[0] + ".bai"))
+        return any(os.path.exists(c) for c in index_paths(self.path))
 
     def max_read_len(self, first_n=101):
         """Largest query length among the first records of the file (the sample's READLEN)."""

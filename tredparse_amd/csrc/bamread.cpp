@@ -1,4 +1,4 @@
-// libtredbam.so -- BGZF / BAM / BAI reader behind include/tredbam.h (host only, zlib).
+// libtredbam.so -- BGZF / BAM / BAI / CSI reader behind include/tredbam.h (host only, zlib).
 //
 // The file layer of the read-selection front end: what the reference takes from
 // pysam/htslib at bam_parser.py:206,226,333,384,404-407.  Written against the SAM specification (sections
@@ -40,8 +40,10 @@ uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | ((uint64_t)le32(p +
 // into the map when the contig is first queried, the linear index is read in place: a whole-genome .bai is ~8 MB of
 // which a sample's queries touch a few contigs' bins and a handful of linear entries -- copying all of it into maps and
 // vectors per sample was a millisecond of every synthetic sample's plan (1.1 MB .bai) and several of a real one's.
+// A .csi has no linear index: its bins carry their own `loffset` instead (loff), and lin stays empty.
 struct RefIndex {
     std::unordered_map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
+    std::unordered_map<uint32_t, uint64_t> loff;   // CSI only: bin -> virtual offset of the first record overlapping it
     bool bins_parsed = false;
     size_t bins_at = 0;             // offset of the contig's first bin record
     int32_t n_bin = 0;
@@ -115,7 +117,11 @@ struct tredbam {
     uint64_t first_record = 0;
     // index
     bool index_loaded = false;
-    std::vector<uint8_t> bai;            // the .bai file's bytes when it could not be mapped
+    // a .csi instead of a .bai (SAM spec 5.2 / CSIv1): bins of min_shift / depth, no linear index.  Its bytes are the
+    // inflated file in `bai` (a BGZF file cannot be mapped and read in place)
+    bool csi = false;
+    int32_t min_shift = 14, depth = 5;
+    std::vector<uint8_t> bai;            // the .bai file's bytes when it could not be mapped; the inflated .csi
     const uint8_t* bai_p = nullptr;      // the .bai file's bytes (RefIndex points into them): mapped read-only, so that only the
     size_t bai_n = 0;                    //   pages a sample's queries touch are ever looked at (1.1 MB - 8 MB per file), or `bai`
     bool bai_mapped = false;
@@ -414,17 +420,103 @@ int emit_record(tredbam* b, int32_t* endp, bool store) {
     return 0;
 }
 
+// A .csi (CSIv1): the whole file is one BGZF stream, inflated here into b->bai at once; then "CSI\1", min_shift, depth,
+// l_aux, aux, n_ref and per contig n_bin bins of (bin, loffset, n_chunk, chunks) -- only the chunk counts are looked at
+// here, contig_index parses a contig's bins on first use.  The pseudo-bin of the statistics and n_no_coor are skipped.
+int load_csi(tredbam* b, int fd) {
+    std::vector<uint8_t> file;
+    {
+        uint8_t tmp[65536];
+        ssize_t g;
+        while ((g = read(fd, tmp, sizeof tmp)) > 0) file.insert(file.end(), tmp, tmp + g);
+    }
+    std::vector<uint8_t>& d = b->bai;
+    d.clear();
+    for (size_t at = 0; at < file.size();) {
+        const uint8_t* h = file.data() + at;
+        if (file.size() - at < 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return fail(b, -4, "bad CSI: not BGZF");
+        const size_t xlen = le16(h + 10);
+        if (file.size() - at < 12 + xlen) return fail(b, -4, "truncated CSI");
+        int bsize = -1;
+        for (size_t p = 0; p + 4 <= xlen;) {
+            const size_t slen = le16(h + 12 + p + 2);
+            if (h[12 + p] == 66 && h[12 + p + 1] == 67 && p + 6 <= xlen) bsize = le16(h + 12 + p + 4);
+            p += 4 + slen;
+        }
+        if (bsize < 0 || (size_t)bsize + 1 < 12 + xlen + 8) return fail(b, -4, "bad CSI: BGZF block without BC field");
+        const size_t clen = (size_t)bsize + 1;
+        if (file.size() - at < clen) return fail(b, -4, "truncated CSI");
+        const uint8_t* comp = h + 12 + xlen;
+        const size_t dlen = clen - 12 - xlen - 8;
+        const uint32_t isize = le32(comp + dlen + 4);
+        if (isize > 65536) return fail(b, -4, "bad CSI: BGZF block claims %u bytes", isize);
+        const size_t o = d.size();
+        d.resize(o + isize + tredbam_inflate::SLACK);
+        if (isize > 0 && !inflate_dispatch(comp, dlen, d.data() + o, isize, b->inflate_tables)) {
+            z_stream zs;
+            memset(&zs, 0, sizeof zs);
+            if (inflateInit2(&zs, -15) != Z_OK) return fail(b, -7, "inflateInit2 failed");
+            zs.next_in = const_cast<uint8_t*>(comp);
+            zs.avail_in = (uInt)dlen;
+            zs.next_out = d.data() + o;
+            zs.avail_out = isize;
+            const int rc = inflate(&zs, Z_FINISH);
+            inflateEnd(&zs);
+            if (rc != Z_STREAM_END || zs.total_out != isize) return fail(b, -4, "bad CSI: inflate failed");
+        }
+        if (tredbam_crc::crc32(0, d.data() + o, isize) != le32(comp + dlen)) return fail(b, -4, "bad CSI: CRC mismatch");
+        d.resize(o + isize);
+        at += clen;
+    }
+    b->bai_p = d.data();
+    b->bai_n = d.size();
+    if (d.size() < 16 || memcmp(d.data(), "CSI\1", 4) != 0) return fail(b, -4, "bad CSI magic");
+    const int32_t min_shift = (int32_t)le32(d.data() + 4), depth = (int32_t)le32(d.data() + 8), l_aux = (int32_t)le32(d.data() + 12);
+    // (positions are 32-bit: min_shift + 3 depth beyond 62 would overflow the bin arithmetic, not describe a file)
+    if (min_shift < 1 || min_shift > 32 || depth < 0 || depth > 9 || min_shift + 3 * depth > 62) return fail(b, -4, "bad CSI header");
+    if (l_aux < 0 || 16 + (size_t)l_aux + 4 > d.size()) return fail(b, -4, "truncated CSI");
+    size_t p = 16 + (size_t)l_aux;
+    const int32_t n_ref = (int32_t)le32(d.data() + p); p += 4;
+    b->min_shift = min_shift;
+    b->depth = depth;
+    b->index.assign((size_t)std::max(n_ref, 0), RefIndex());
+    for (int32_t t = 0; t < n_ref; ++t) {
+        if (p + 4 > d.size()) return fail(b, -4, "truncated CSI");
+        const int32_t n_bin = (int32_t)le32(d.data() + p); p += 4;
+        if (n_bin < 0) return fail(b, -4, "truncated CSI");
+        b->index[t].bins_at = p;
+        b->index[t].n_bin = n_bin;
+        for (int32_t k = 0; k < n_bin; ++k) {
+            if (p + 16 > d.size()) return fail(b, -4, "truncated CSI");
+            const int32_t n_chunk = (int32_t)le32(d.data() + p + 12); p += 16;
+            if (n_chunk < 0 || p + 16 * (size_t)n_chunk > d.size()) return fail(b, -4, "truncated CSI");
+            p += 16 * (size_t)n_chunk;
+        }
+    }
+    b->csi = true;
+    b->index_loaded = true;
+    return 0;
+}
+
+// The index next to the BAM: <bam>.bai, <stem>.bai, <bam>.csi, <stem>.csi, the first that opens.  (htslib looks for the
+// .csi first; a .bai first keeps every file that has one read as before -- DESIGN 1.)
 int load_index(tredbam* b) {
     if (b->index_loaded) return 0;
-    std::string cand[2] = {b->path + ".bai", b->path};
-    const size_t dot = cand[1].rfind('.');
-    if (dot != std::string::npos) cand[1] = cand[1].substr(0, dot);
-    cand[1] += ".bai";
+    std::string stem = b->path;
+    const size_t dot = stem.rfind('.');
+    if (dot != std::string::npos) stem = stem.substr(0, dot);
+    const std::string cand[4] = {b->path + ".bai", stem + ".bai", b->path + ".csi", stem + ".csi"};
     if (b->bai_mapped) { munmap(const_cast<uint8_t*>(b->bai_p), b->bai_n); b->bai_mapped = false; }   // (an earlier, refused index)
-    int fd = -1;
-    for (const std::string& c : cand)
-        if ((fd = open(c.c_str(), O_RDONLY | O_CLOEXEC)) >= 0) break;
+    b->csi = false;
+    int fd = -1, which = 0;
+    for (; which < 4; ++which)
+        if ((fd = open(cand[which].c_str(), O_RDONLY | O_CLOEXEC)) >= 0) break;
     if (fd < 0) return fail(b, -4, "no .bai index next to %s", b->path.c_str());
+    if (which >= 2) {
+        const int rc = load_csi(b, fd);
+        close(fd);
+        return rc;
+    }
     struct Bytes { const uint8_t* p; size_t n; const uint8_t* data() const { return p; } size_t size() const { return n; } } d{nullptr, 0};
     {
         struct stat st;
@@ -480,8 +572,21 @@ const RefIndex& contig_index(tredbam* b, int32_t tid) {
         const uint8_t* d = b->bai_p;
         size_t p = ix.bins_at;
         ix.bins.reserve((size_t)ix.n_bin * 2);
+        // (CSI: the pseudo-bin of the statistics is numbered one past the last bin of the scheme)
+        const uint32_t pseudo = (uint32_t)((((uint64_t)1 << (3 * (b->depth + 1))) - 1) / 7 + 1);
         for (int32_t k = 0; k < ix.n_bin; ++k) {
             const uint32_t bin = le32(d + p);
+            if (b->csi) {
+                const int32_t n_chunk = (int32_t)le32(d + p + 12);
+                if (bin != pseudo) {
+                    ix.loff[bin] = le64(d + p + 4);
+                    auto& v = ix.bins[bin];
+                    v.reserve((size_t)n_chunk);
+                    for (int32_t c = 0; c < n_chunk; ++c) v.emplace_back(le64(d + p + 16 + 16 * c), le64(d + p + 24 + 16 * c));
+                }
+                p += 16 + 16 * (size_t)n_chunk;
+                continue;
+            }
             const int32_t n_chunk = (int32_t)le32(d + p + 4); p += 8;
             auto& v = ix.bins[bin];
             v.reserve((size_t)n_chunk);
@@ -507,7 +612,7 @@ int region_chunks(tredbam* b, int32_t tid, int64_t& start, int64_t& end, std::ve
     uint64_t min_off = 0;
     if (ix.n_lin > 0) min_off = ix.linear(std::min<size_t>((size_t)(start >> 14), ix.n_lin - 1));
     // reg2bins of the 5-level scheme over [start, max(end, start + 1))
-    const int64_t e1 = std::max(end, start + 1) - 1;
+    int64_t e1 = std::max(end, start + 1) - 1;
     std::vector<std::pair<uint64_t, uint64_t>> chunks;
     auto add_bin = [&](uint32_t bin) {
         auto it = ix.bins.find(bin);
@@ -515,11 +620,35 @@ int region_chunks(tredbam* b, int32_t tid, int64_t& start, int64_t& end, std::ve
         for (const auto& ch : it->second)
             if (ch.second > min_off) chunks.emplace_back(std::max(ch.first, min_off), ch.second);
     };
-    add_bin(0);
-    const int shifts[5] = {26, 23, 20, 17, 14};
-    const uint32_t bases[5] = {1, 9, 73, 585, 4681};
-    for (int l = 0; l < 5; ++l)
-        for (int64_t k = start >> shifts[l]; k <= e1 >> shifts[l]; ++k) add_bin(bases[l] + (uint32_t)k);
+    if (b->csi) {
+        // the general reg2bins: level l = 0 .. depth has shift min_shift + 3 (depth - l), its bins start at
+        // ((1 << 3l) - 1) / 7.  min_off as htslib takes it for a CSI: the loffset of the deepest bin that holds `start`,
+        // else of the nearest bin left of it on that level, else of its parent (every one of them is a bin whose first
+        // record comes no later than the first record that overlaps `start`)
+        const int ms = b->min_shift, dp = b->depth;
+        const int64_t maxpos = (int64_t)1 << (ms + 3 * dp);
+        if (start >= maxpos) { merged.clear(); return 0; }
+        e1 = std::min(e1, maxpos - 1);
+        uint32_t bin = (uint32_t)(((((uint64_t)1 << (3 * dp)) - 1) / 7) + (uint64_t)(start >> ms));
+        for (;;) {
+            const auto it = ix.loff.find(bin);
+            if (it != ix.loff.end()) { min_off = it->second; break; }
+            if (bin == 0) break;
+            const uint32_t first = (((bin - 1) >> 3) << 3) + 1;     // the first child of this bin's parent
+            bin = bin > first ? bin - 1 : (bin - 1) >> 3;
+        }
+        for (int l = 0; l <= dp; ++l) {
+            const int shift = ms + 3 * (dp - l);
+            const uint32_t base = (uint32_t)((((uint64_t)1 << (3 * l)) - 1) / 7);
+            for (int64_t k = start >> shift; k <= e1 >> shift; ++k) add_bin(base + (uint32_t)k);
+        }
+    } else {
+        add_bin(0);
+        const int shifts[5] = {26, 23, 20, 17, 14};
+        const uint32_t bases[5] = {1, 9, 73, 585, 4681};
+        for (int l = 0; l < 5; ++l)
+            for (int64_t k = start >> shifts[l]; k <= e1 >> shifts[l]; ++k) add_bin(bases[l] + (uint32_t)k);
+    }
     std::sort(chunks.begin(), chunks.end());
     for (const auto& ch : chunks) {
         if (!merged.empty() && ch.first <= merged.back().second) merged.back().second = std::max(merged.back().second, ch.second);
@@ -1460,8 +1589,17 @@ int64_t tredbam_plan(tredbam* b, const tredbam_site* sites, int32_t n_sites, con
         if (tid < (int32_t)b->index.size()) {
             const RefIndex& lin = b->index[tid];
             const size_t w = (size_t)((std::max<int64_t>(end, 1) - 1) >> 14) + 2;
+            if (b->csi) {
+                // no linear index: the loffset of the first leaf bin that starts at or behind window w's start, when that
+                // bin is in the index (then some record lies in it: its loffset is the first record overlapping it)
+                const int ms = b->min_shift, dp = b->depth;
+                const int64_t q = (int64_t)w << 14, leaf = (q + ((int64_t)1 << ms) - 1) >> ms;
+                if (q < ((int64_t)1 << (ms + 3 * dp))) {
+                    const auto it = lin.loff.find((uint32_t)(((((uint64_t)1 << (3 * dp)) - 1) / 7) + (uint64_t)leaf));
+                    if (it != lin.loff.end() && it->second != 0) cap = it->second;
+                }
             // (an entry equal to its predecessor is a window without a record of its own, filled in from before it)
-            if (w < lin.n_lin && lin.linear(w) != 0 && lin.linear(w) > lin.linear(w - 1)) cap = lin.linear(w);
+            } else if (w < lin.n_lin && lin.linear(w) != 0 && lin.linear(w) > lin.linear(w - 1)) cap = lin.linear(w);
         }
         for (const auto& ch : merged) {
             const int64_t last = (int64_t)(std::min(ch.second, cap) >> 16);

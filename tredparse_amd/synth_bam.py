@@ -15,8 +15,8 @@ BGZF/BAI reader, read selection, pair-length extraction, depth) is exercised, no
     some have a secondary copy -- the flags depth (:404-411) and PEextractor (:334-340) look at;
   * per-base substitutions, rare N.
 
-`write_bam` emits BGZF blocks (records never straddle a block) and the .bai (bins + 16 kb linear index) per the SAM
-specification.  `expected_scan` derives, in numpy and from the record table alone, what the front end has to find
+`write_bam` emits BGZF blocks (records never straddle a block) and the .bai (bins + 16 kb linear index) or a .csi per the
+SAM specification.  `expected_scan` derives, in numpy and from the record table alone, what the front end has to find
 for a locus (selected reads in order, depth, pair lengths): the independent statement tests compare the native
 scan with, and the source of the packed batch "for the same seed".
 """
@@ -26,6 +26,7 @@ import zlib
 
 import numpy as np
 
+from .bamio import csi_bytes
 from .synth import SynthParams, _COMP, encode, load_loci
 
 CONTIGS = ["chr{}".format(i) for i in range(1, 23)] + ["chrX", "chrY", "chr22_KI270733v1_random", "chrUn_GL000220v1"]
@@ -435,8 +436,10 @@ WRITE_SLICE = 150000          # records encoded at a time (the index matrices of
 
 
 def write_bam(path, recs, sample="s", level=1, block=0xff00, split_records=False, decoys=0.0, decoy_seed=1, no_seq=None, aux=b"",
-              lengths=None):
-    """Write `recs` (sorted) as <path> and <path>.bai.  Returns the number of uncompressed bytes.  split_records: cut the
+              lengths=None, index="bai", csi_shift=14):
+    """Write `recs` (sorted) as <path> and its index: <path>.bai (index="bai"), <path>.csi with bins of 1 << csi_shift bases
+    at the deepest level ("csi": bamio.csi_bytes) or both ("both").  Returns the number of uncompressed bytes.  split_records: cut
+    the
     record stream into blocks of `block` bytes wherever that falls (records then straddle blocks, as in files written by
     samtools) instead of at record boundaries.  decoys: that share of the reads gets base qualities that read as the
     head of a BAM record of the read's contig (tests of the device walk's guessed record starts: DESIGN 4.5).
@@ -444,6 +447,8 @@ def write_bam(path, recs, sample="s", level=1, block=0xff00, split_records=False
     no_seq: a mask of records written without sequence and qualities (l_seq 0).  aux: bytes of optional fields (tag, type,
     value ...) appended to every record, as aligners leave them (NM, MD, AS, RG ...).  lengths: every record's own sequence
     length (<= the codes' width; trim_records makes the CIGARs agree): reads trimmed before alignment."""
+    if index not in ("bai", "csi", "both"):
+        raise ValueError("index must be 'bai', 'csi' or 'both'")
     n = len(recs)
     rend = recs.ref_end
     end_for_bin = np.where(rend > recs.pos, rend, recs.pos + 1)
@@ -479,7 +484,7 @@ def write_bam(path, recs, sample="s", level=1, block=0xff00, split_records=False
         which = np.where(off >= len(blob), len(starts), which)
         inside = np.where(which < len(starts), off - which * block, 0)
         v = (co[which] << 16) | inside
-        _write_bai(path + ".bai", recs.tid, recs.pos.astype(np.int64), end_for_bin, bins, v[:-1], v[1:])
+        _write_index(path, index, csi_shift, recs, end_for_bin, bins, v[:-1], v[1:])
         return len(blob)
     cuts = [0]
     while cuts[-1] < n:
@@ -510,8 +515,17 @@ def write_bam(path, recs, sample="s", level=1, block=0xff00, split_records=False
     vend = voff[1:].copy()
     for b in cuts[1:-1]:
         vend[b - 1] = voff[b]
-    _write_bai(path + ".bai", recs.tid, recs.pos.astype(np.int64), end_for_bin, bins, voff[:-1], vend)
+    _write_index(path, index, csi_shift, recs, end_for_bin, bins, voff[:-1], vend)
     return int(off[-1])
+
+
+def _write_index(path, index, csi_shift, recs, end, bins, vbeg, vend):
+    if index in ("bai", "both"):
+        _write_bai(path + ".bai", recs.tid, recs.pos.astype(np.int64), end, bins, vbeg, vend)
+    if index in ("csi", "both"):
+        with open(path + ".csi", "wb") as fp:
+            fp.write(csi_bytes([CONTIG_LEN] * len(CONTIGS), recs.tid, recs.pos, end, vbeg, vend,
+                               (recs.flag & FUNMAP) != 0, min_shift=csi_shift))
 
 
 def _write_bai(path, tid, pos, end, bins, vbeg, vend):
