@@ -10,16 +10,17 @@ results stay on the device.
 How it runs
   * under torch.distributed.run (RANK in the environment): this process is one rank = one GPU; RCCL carries the
     barrier and the max-over-ranks wall time only -- samples are independent, there is no data-path collective;
-  * started directly: this process is a launcher that NEVER touches a GPU.  For every rank count n of the sweep
-    (1, 2, 4, 8 up to the GPUs visible, and --gpus itself) it starts n child ranks (tredparse_amd.shard.spawn_ranks:
-    HIP_VISIBLE_DEVICES = one device per child, rank r on device r mod visible), collects their per-rank records,
-    runs the end-to-end legs from BAM files (run_e2e: the host-only leg and THE plan of shard.driver_plan, steady state),
-    the extra one-GPU legs (streamed, configs[4], 100 / 250 bp), and times the CPU baseline on 1 core and on all
-    host cores.
+  * started directly: this process is a launcher that NEVER touches a GPU.  It starts --gpus child ranks
+    (tredparse_amd.shard.spawn_ranks: HIP_VISIBLE_DEVICES = one device per child, rank r on device r mod visible) and
+    collects rank 0's line and the per-rank records: the headline.  That is all a plain run does.
+  * --full adds everything else the benchmark measures: the same for every rank count n of the sweep (1, 2, 4, 8 up to
+    the GPUs visible), the end-to-end legs from BAM files (run_e2e: the host-only leg and THE plan of
+    shard.driver_plan, steady state), the extra one-GPU legs (streamed, configs[4], 100 / 250 bp), and the CPU baseline
+    on 1 core and on all host cores.
 
-Output: the LAST stdout line is one compact JSON object (< 4 KB, compact_line): the contract's keys, `roofline`,
-`cpu_baseline`, `end_to_end`, one small object per leg.  The full record -- per-rank and per-driver detail, counters,
-notes, every plan of an --e2e-sweep -- goes to bench_detail.json next to this script (and to stderr).
+Output: the LAST stdout line is one compact JSON object (< 4 KB, compact_line): the contract's keys, `roofline`, and
+with --full `cpu_baseline`, `end_to_end`, one small object per leg.  The full record -- per-rank and per-driver detail,
+counters, notes, every plan of an --e2e-sweep -- goes to bench_detail.json next to this script (and to stderr).
 `--dump-outputs DIR` also writes what the headline's last timed step computed as DIR/<name>.npy (dump_outputs), so
 that two builds can be compared output for output: the inputs depend on the arguments alone.
 
@@ -1090,7 +1091,8 @@ def launcher_main(args):
     scaling = []
     # TRED_VIRTUAL_GPUS=V (shard.virtual_gpus): the box's devices counted as V -- the rehearsal of an 8-GPU run on one GPU
     real = 1 if args.stub else shard.real_gpus(n_devices)
-    for n in sweep_counts(args.gpus, n_devices, not args.no_sweep):
+    # a plain run is the headline alone: --gpus ranks once; --full adds the sweep, the from-BAM and extra legs and the CPU baseline
+    for n in sweep_counts(args.gpus, n_devices, args.full and not args.no_sweep):
         line, ranks = run_ranks(args, n, n_devices, dump=args.dump_outputs if n == args.gpus else None)
         lines[n] = line
         rec = {"n": n, "value": line["value"], "unit": line["unit"], "ms_per_step": line["ms_per_step"],
@@ -1105,7 +1107,7 @@ def launcher_main(args):
     if real < n_devices:
         out["virtual_gpus"] = {"counted": n_devices, "physical": real,
                                "note": "TRED_VIRTUAL_GPUS: every rank and driver is real, the devices are not -- a rehearsal, no scaling point"}
-    if args.e2e_samples > 0 and not args.stub:
+    if args.full and args.e2e_samples > 0 and not args.stub:
         # the product path from BAM files at every device count of the sweep that the box really has (a 1-GPU box:
         # n = 1 only); the line's own record is that of --gpus
         counts = sorted(set(r["n"] for r in scaling if not r.get("oversubscribed") or (real < n_devices and r["n"] <= n_devices)) |
@@ -1120,12 +1122,12 @@ def launcher_main(args):
                 rec = e2e[r["n"]]
                 r["end_to_end"] = {k: rec[k] for k in ("value", "unit", "drivers", "devices", "samples", "seconds",
                                                        "host_threads_per_driver", "outputs_identical") if k in rec}
-    if args.e2e_samples > 0 and args.e2e_wgs_samples > 0 and not args.stub:
+    if args.full and args.e2e_samples > 0 and args.e2e_wgs_samples > 0 and not args.stub:
         try:
             out["end_to_end_wgs"] = run_e2e_wgs(args)
         except Exception as e:                  # (a stated second number: its failure must not take the line down)
             out["end_to_end_wgs"] = {"error": str(e)}
-    if args.legs and not args.stub:
+    if args.full and args.legs and not args.stub:
         # the configurations that otherwise only have correctness tests, one rank each on device 0: BASELINE
         # configs[4] and the other read lengths (their own sw_cont_kernel instantiations)
         out["legs"] = []
@@ -1166,7 +1168,7 @@ def launcher_main(args):
                                 "mix_ceiling_frac": r.get("mix_ceiling_frac"),
                                 "roofline": {k: r[k] for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "mix_ceiling_frac",
                                                                "avg_launch_ms", "lane_occupancy", "effective_TCUPS")}})
-    if not args.no_cpu_baseline and not args.stub:
+    if args.full and not args.no_cpu_baseline and not args.stub:
         loci, batch = make_batch(args, 0, 1)
         from tredparse_amd import shard as _shard
         cores = args.cpu_cores or _shard.usable_cpus()      # the cgroup quota, not the CPUs merely visible
@@ -1201,18 +1203,21 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="config3",
                     help="config3 = BASELINE configs[2] (the headline); config5 = configs[4] (100x, expanded alleles)")
     ap.add_argument("--seed", type=int, default=20260101)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the 1/2/4/8 rank sweep, the end-to-end legs from BAM files, "
+                         "the extra one-GPU legs (--legs) and the CPU baseline; a plain run times the --gpus ranks alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds per CPU baseline leg")
     ap.add_argument("--cpu-cores", type=int, default=0, help="worker processes of the all-core leg (0: all)")
-    ap.add_argument("--no-sweep", action="store_true", help="only --gpus ranks, no 1/2/4/8 sweep")
+    ap.add_argument("--no-sweep", action="store_true", help="--full: only --gpus ranks, no 1/2/4/8 sweep")
     ap.add_argument("--rank-timeout", type=float, default=1500.0)
     ap.add_argument("--stub", action="store_true", help="launcher self-test: ranks do no GPU work")
     ap.add_argument("--e2e-samples", type=int, default=4096,
-                    help="BAM files per GPU of the end-to-end legs (0: skip them): the same number at every device count")
+                    help="--full: BAM files per GPU of the end-to-end legs (0: skip them): the same number at every device count")
     ap.add_argument("--e2e-distinct", type=int, default=512,
                     help="distinct synthetic BAMs made; a larger cohort gets the rest as hard links under their own sample keys")
     ap.add_argument("--e2e-wgs-samples", type=int, default=64,
-                    help="BAM files of the whole-genome-shaped leg (0: skip it): the loci AND 30x background over every alternative "
+                    help="--full: BAM files of the whole-genome-shaped leg (0: skip it): the loci AND 30x background over every alternative "
                          "region's index window")
     ap.add_argument("--e2e-wgs-distinct", type=int, default=8, help="distinct files among them (the rest are hard links)")
     ap.add_argument("--e2e-repeats", type=int, default=3, help="how often the planned end-to-end leg is run (value = the median)")
@@ -1223,7 +1228,7 @@ def main():
     ap.add_argument("--e2e-threads", type=int, default=0, help="host threads per driver in the end-to-end leg (0: cores / drivers)")
     ap.add_argument("--e2e-drivers", type=int, default=0, help="driver processes per GPU in the planned end-to-end leg (0: shard.driver_plan's rule)")
     ap.add_argument("--legs", default="streamed:4,config5:150:200,config3:100:500,config3:250:500",
-                    help="extra one-GPU legs workload:readlen:samples, comma separated ('' for none)")
+                    help="--full: extra one-GPU legs workload:readlen:samples, comma separated ('' for none)")
     ap.add_argument("--e2e-gpu-inflate", choices=("0", "1"), default="1",
                     help="the planned end-to-end leg has the BAMs' BGZF blocks inflated on the GPU (tred.run_many inflate_device)")
     ap.add_argument("--e2e-gpu-select", choices=("0", "1"), default="1",
@@ -1235,7 +1240,7 @@ def main():
     ap.add_argument("--e2e-inflate-batch", type=int, default=36, help="samples per GPU batch (= per decode + walk + select call) in the planned leg: 36 fills the device (55.8 / 60.6 / 64.0 k genotypes/s at 12 / 24 / 36; 3.8 GB of pinned staging per GPU); legs without the selection on the device keep 12")
     ap.add_argument("--streamed", type=int, default=0,
                     help="also time the step fed from pinned host memory: this many distinct batches, double-buffered "
-                         "copy-in beside the kernels (the default run adds it as the `streamed` leg with 4 batches)")
+                         "copy-in beside the kernels (--full adds it as the `streamed` leg with 4 batches)")
     ap.add_argument("--e2e-python-writer", action="store_true",
                     help="end-to-end legs through the Python result dicts and writers instead of the native writer (A/B)")
     ap.add_argument("--e2e-only", action="store_true", help="run the end-to-end legs alone and print one line per leg (tuning)")

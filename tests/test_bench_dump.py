@@ -73,9 +73,35 @@ def test_only_the_headline_ranks_dump(monkeypatch, tmp_path):
     monkeypatch.setattr(bench, "run_ranks", fake_run_ranks)
     monkeypatch.setattr(bench, "ROOT", str(tmp_path))
     args = argparse.Namespace(stub=True, e2e_only=False, gpus=2, no_sweep=False, e2e_samples=0, e2e_wgs_samples=0, legs="",
-                              no_cpu_baseline=True, dump_outputs=str(tmp_path / "d"))
+                              no_cpu_baseline=True, dump_outputs=str(tmp_path / "d"), full=True)
     bench.launcher_main(args)
     assert seen == [(1, None), (2, str(tmp_path / "d"))]
+
+
+def test_a_plain_run_is_the_headline_alone(monkeypatch, tmp_path):
+    """Without --full: the --gpus ranks once (they dump), and none of the sweep, the from-BAM legs, the extra legs or the
+    CPU baseline, whatever their own options say."""
+    import bench
+    from tredparse_amd import shard
+    seen = []
+
+    def fake_run_ranks(args, n, n_devices, dump=None):
+        seen.append((n, dump))
+        return {"value": 1.0, "unit": "genotypes/s", "ms_per_step": 1.0, "n_gpus": n}, []
+
+    def never(*a, **k):
+        raise AssertionError("a plain run ran more than the headline")
+
+    monkeypatch.setattr(bench, "run_ranks", fake_run_ranks)
+    for name in ("run_e2e", "run_e2e_wgs", "cpu_baselines", "make_batch"):
+        monkeypatch.setattr(bench, name, never)
+    monkeypatch.setattr(shard, "visible_gpus", lambda: 1)
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    args = argparse.Namespace(stub=False, e2e_only=False, gpus=1, no_sweep=False, e2e_samples=4096, e2e_wgs_samples=64,
+                              legs="streamed:4,config5:150:200", no_cpu_baseline=False, dump_outputs=str(tmp_path / "d"),
+                              full=False)
+    bench.launcher_main(args)
+    assert seen == [(1, str(tmp_path / "d"))]
 
 
 def _bench(out, steps):

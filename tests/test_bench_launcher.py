@@ -20,7 +20,7 @@ def _run(*extra):
 
 
 def test_launcher_runs_n_ranks_and_sums_their_units():
-    rec = _run("--gpus", "2")
+    rec = _run("--gpus", "2", "--full")
     assert rec["n_gpus"] == 2 and rec["stub"] is True
     # stub ranks: 10 samples x 30 loci x 2 steps each, rank r takes 0.05 * (r + 1) s -> 1200 units / 0.1 s
     assert abs(rec["value"] - 12000.0) < 1e-6
@@ -32,9 +32,16 @@ def test_launcher_runs_n_ranks_and_sums_their_units():
 
 
 def test_no_sweep_runs_only_the_requested_rank_count():
-    rec = _run("--gpus", "3", "--no-sweep")
+    rec = _run("--gpus", "3", "--no-sweep", "--full")
     assert rec["n_gpus"] == 3 and [s["n"] for s in rec["scaling_sweep"]] == [3]
     assert len(rec["scaling_sweep"][0]["ranks"]) == 3
+
+
+def test_a_plain_run_starts_the_requested_ranks_once():
+    """Without --full the launcher times the --gpus ranks alone: no sweep of other rank counts."""
+    rec = _run("--gpus", "2")
+    assert rec["n_gpus"] == 2 and abs(rec["value"] - 12000.0) < 1e-6
+    assert [s["n"] for s in rec["scaling_sweep"]] == [2] and [r["rank"] for r in rec["scaling_sweep"][0]["ranks"]] == [0, 1]
 
 
 def test_eight_ranks_of_a_thousand_samples_each_configs3_shape():

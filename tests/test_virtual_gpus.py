@@ -44,7 +44,7 @@ def test_bench_with_four_virtual_gpus(tmp_path):
     t0 = time.time()
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--samples", "40",
                         "--e2e-samples", "8", "--e2e-distinct", "8", "--e2e-seconds", "2", "--e2e-repeats", "2", "--e2e-inflate-batch", "4",
-                        "--e2e-drivers", "1", "--legs", "", "--no-cpu-baseline", "--e2e-wgs-samples", "0"],
+                        "--e2e-drivers", "1", "--legs", "", "--no-cpu-baseline", "--e2e-wgs-samples", "0", "--full"],
                        env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
     seconds = time.time() - t0
     assert p.returncode == 0, p.stderr[-3000:]

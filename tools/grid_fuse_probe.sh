@@ -9,7 +9,7 @@ O=gpurun_out/r06_grid_fuse_probe.txt
 SRC=tredparse_amd/csrc/grid.hip
 cp $SRC /tmp/grid_tree.hip
 run() {
-  timeout 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --e2e-samples 0 --no-sweep --legs config3:100:500 2>/dev/null | tail -1 | python -c "
+  timeout 400 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --e2e-samples 0 --no-sweep --legs config3:100:500 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernels_ms_per_step']

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06_grid_waves_ab.txt
 echo "# bench.py --steps 5 --warmup 2 --legs config3:100:500; per build: grid kernels' ms per step at 150 bp (30 000 units) | at 100 bp (15 000 units)" > $O
 run() {
-  timeout 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --e2e-samples 0 --no-sweep --legs config3:100:500 2>/dev/null | tail -1 | python -c "
+  timeout 400 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --e2e-samples 0 --no-sweep --legs config3:100:500 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernels_ms_per_step']

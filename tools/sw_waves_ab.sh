@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06_sw_waves_ab2.txt
 echo "# bench.py --steps 5 --warmup 2 --samples 1000 --legs config3:100:500,config3:250:500 (headline = 150 bp); per build: value, ms/step, frac" > $O
 run() {
-  timeout 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --e2e-samples 0 --no-sweep --legs config3:100:500,config3:250:500 2>/dev/null | tail -1 | python -c "
+  timeout 400 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --e2e-samples 0 --no-sweep --legs config3:100:500,config3:250:500 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('$1', '150bp value {:.0f} ms/step {:.3f} sw {:.3f} frac {:.4f} |'.format(d['value'], d['ms_per_step'], d['kernels_ms_per_step']['sw_ladder'], d['roofline']['frac']), ' | '.join('{} value {:.0f} ms/step {:.3f} frac {:.4f}'.format(l['leg'], l['value'], l['ms_per_step'], l['frac']) for l in d['legs'] if 'value' in l))" >> $O
