@@ -282,21 +282,40 @@ def test_reads_of_321_to_470_bp_take_the_32_rows_per_lane_instantiation(ctx):
     assert (t2 == _lib.TAG_FULL).sum() > 20 and (t2 == _lib.TAG_REPT).sum() > 0
 
 
+def _joint_sets(r, u):
+    """Unit u's joint entries as a sorted list, from joint (alleles in bp) and from joint_units (repeat units, share)."""
+    a, b, v, lo, n = r.joint_units
+    s = slice(lo[u], lo[u] + n[u])
+    return sorted(map(tuple, r.joint[u][0].tolist())), r.joint[u][1], sorted(zip(a[s].tolist(), b[s].tolist(), v[s].tolist()))
+
+
+@pytest.mark.parametrize("joint_cap", [512, 1])
 @pytest.mark.parametrize("repeatpairs", [True, False])
-def test_fused_host_call_equals_the_three_separate_calls(tmp_path, repeatpairs):
+def test_fused_host_call_equals_the_three_separate_calls(tmp_path, monkeypatch, repeatpairs, joint_cap):
     """tredgpu_genotype_batch_joint (SW -> tally -> grid with marginals and sparse joint composed on the device, one wait:
     what engine.genotype_packed calls for every product batch) against tredgpu_sw_classify + tredgpu_tally +
-    tredgpu_likelihood_grid_joint one after the other: the same tags, calls, marginals and joint entries bit for bit."""
-    from tredparse_amd import bam_parser, synth_bam
+    tredgpu_likelihood_grid_joint one after the other: the same tags, calls, marginals and joint entries bit for bit.
+    joint_cap 1: every unit with more than one joint entry takes the grow-and-retry path of the joint read-back, and both
+    paths give the entries of a run at the default capacity."""
+    from tredparse_amd import bam_parser, engine as engmod, synth_bam
     from tredparse_amd.engine import Engine, PackedUnits
     from tredparse_amd.meta import TREDsRepo
+    assert engmod.JOINT_CAP == 512
     made = synth_bam.make_bams(str(tmp_path), 3, seed=41, workers=1)
     repo = TREDsRepo("hg38", sites=str(tmp_path / "no_sites"))
     names = [l["name"] for l in synth_bam.bench_loci()]
     scans = [bam_parser.scan_sample(path, repo, names) for _, path, _ in made]
     b = PackedUnits.from_scans([(s, list(range(len(names)))) for s in scans], repeatpairs=repeatpairs)
     eng = Engine(0)
+    base = eng.genotype_packed(b)
+    monkeypatch.setattr(engmod, "JOINT_CAP", joint_cap)
     one, three = eng.genotype_packed(b), eng._genotype_packed_stepwise(b)
+    monkeypatch.undo()
+    assert (base.joint_units[4] > 1).sum() > 60           # (units that retry at capacity 1)
+    for r in (one, three):
+        assert r.calls.tobytes() == base.calls.tobytes()
+        for u in np.nonzero(base.calls["status"] == 0)[0]:
+            assert _joint_sets(r, u) == _joint_sets(base, u), u
     assert b.n_units == 90 and b.n_reads > 5000
     for key in ("tag", "h", "score", "rept", "marg"):
         assert np.array_equal(getattr(one, key), getattr(three, key)), key

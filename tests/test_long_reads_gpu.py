@@ -179,6 +179,20 @@ def test_bounds(lctx, by_period):
         lctx.sw_classify(_lib.MEM_DEVICE, 0, 0, 0, 1, 0, 0, 1, _lib.default_sw_params(), 0, 0, 0)
     with pytest.raises(_lib.TredGpuError, match="register shorter ladders"):
         lctx.set_long_reads(False)
+    # hist_stride of the routed calls (a 600 bp read takes the long path): genotype_batch checks it against every registered
+    # ladder (the library's max_ladder_units), genotype_batch_joint against the batch's own ladders (the fused call's per-unit check)
+    lctx.set_ladders([(hd["prefix"], "CAG", hd["suffix"], 50), (hd["prefix"], "CAG", hd["suffix"], 300)])
+    packed, woff, rlen = _lib.pack_reads([read[:600]])
+    uro, ul, units, lens = np.array([0, 1], np.int32), np.zeros(1, np.int32), np.zeros(1, _lib.UNIT_DTYPE), np.zeros(1, np.int32)
+    tag, h, sc, calls = np.zeros(1, np.uint8), np.zeros(1, np.int16), np.zeros(1, np.int16), np.zeros(1, _lib.CALL_DTYPE)
+    hist = [np.zeros((1, 100), np.int32) for _ in range(3)]
+    with pytest.raises(_lib.TredGpuError, match="^hist_stride 100 must exceed the max_units 300 of ladder 1$"):
+        lctx.genotype_batch(_lib.MEM_HOST, packed, woff, rlen, 1, uro, ul, units, 1, _lib.default_sw_params(), None, lens, 0,
+                            lens, 0, tag, h, sc, 100, *hist, calls)
+    marg, joff, trip = np.zeros((1, 2, 302), np.float64), np.array([0, 8], np.int64), np.zeros((8, 3), np.float64)
+    with pytest.raises(_lib.TredGpuError, match="^hist_stride 50 must exceed the max_units 50 of ladder 0$"):
+        lctx.genotype_batch_joint(packed, woff, rlen, 1, uro, ul, units, 1, _lib.default_sw_params(), None, lens, 0, lens, 0,
+                                  tag, h, sc, 50, hist[2], calls, marg, 302, joff, trip, np.zeros(1, np.int32), np.zeros(1))
     # switched off: today's refusals
     off = _lib.Context(0)
     try:

@@ -63,19 +63,27 @@ def _device_scans(args, engine, batch):
         t.release_inflaters()
 
 
-def test_selection_on_the_device_equals_the_host_scan(cohort, engine):
+@pytest.mark.parametrize("joint_cap", [512, 1])
+def test_selection_on_the_device_equals_the_host_scan(cohort, engine, monkeypatch, joint_cap):
+    """joint_cap 1: the device path's joint read-back grows and retries for every unit with more than one entry; the
+    host's batches it is compared with keep the default capacity."""
+    from tredparse_amd import engine as engmod
+    assert engmod.JOINT_CAP == 512
     for k in t.TIMING:
         t.TIMING[k] = 0
+    monkeypatch.setattr(engmod, "JOINT_CAP", joint_cap)
     got = _device_scans(cohort, engine, batch=4)
+    monkeypatch.undo()
     assert t.TIMING["select_samples"] == len(cohort) and t.TIMING["select_declined"] == 0 and t.TIMING["walk_blocks_fetched"] == 0
-    reads = units = 0
+    reads = units = multi = 0
     for a, s, pieces in got:
         assert getattr(s, "device", None) is not None, a[0]
         bad, r, u = fuzz_select.compare(a, s, pieces, engine)
         assert not bad, (a[0], bad)
         reads += r
         units += u
-    assert reads > 2500 and units > 80
+        multi += sum(int((br.joint_units[4][i0:i0 + len(ks)] > 1).sum()) for br, i0, ks in pieces)
+    assert reads > 2500 and units > 80 and multi > 20
 
 
 def test_a_short_random_campaign(capsys, monkeypatch):

@@ -129,10 +129,11 @@ def test_whole_genome_shaped_sample_keeps_its_rescued_mates(tmp_path):
 
 
 @pytest.mark.gpu
-def test_bam_path_equals_packed_path(tmp_path):
+def test_bam_path_equals_packed_path(tmp_path, monkeypatch):
     """BAM -> CLI driver (native scan, PackedUnits) against the packed-batch path fed straight from the simulation's
-    record table (read strings, depth and pair lengths from expected_scan): identical tredCalls."""
-    from tredparse_amd import tred as tredmod
+    record table (read strings, depth and pair lengths from expected_scan): identical tredCalls.  The Unit path at a joint
+    capacity of 1 (every unit with more than one entry grows and retries) gives the same joint entries."""
+    from tredparse_amd import engine as engmod, tred as tredmod
     from tredparse_amd.engine import Engine, Unit
     from tredparse_amd.models import format_call, pair_summary
     repo = TREDsRepo()
@@ -143,7 +144,7 @@ def test_bam_path_equals_packed_path(tmp_path):
     names = [l["name"] for l in loci]
     tasks = [(key, path, repo, names, 300, False, False, True, True, "ERROR") for key, path, _ in made]
     results = tredmod.run_many(tasks, engine, batch=2, threads=2)
-    n_called = short_ok = 0
+    n_called = short_ok = multi = 0
     for i, ((key, path, h_true), res) in enumerate(zip(made, results)):
         recs, h2 = sb.simulate_sample(500 + i, loci, p)
         assert np.array_equal(h_true, h2)
@@ -152,6 +153,14 @@ def test_bam_path_equals_packed_path(tmp_path):
             reads, depth, gl, tl = sb.expected_scan(recs, l, 150)
             units.append(Unit(repo[l["name"]], 150, [synth.decode(recs.codes[r]) for r in reads], depth, 2, gl, tl))
         direct = engine.genotype(units)
+        monkeypatch.setattr(engmod, "JOINT_CAP", 1)
+        low = engine.genotype(units)
+        monkeypatch.undo()
+        for r, q in zip(direct, low):
+            assert r.call.tobytes() == q.call.tobytes()
+            if r.joint is not None:
+                assert sorted(map(tuple, q.joint[0].tolist())) == sorted(map(tuple, r.joint[0].tolist())) and q.joint[1] == r.joint[1]
+                multi += len(r.joint[0]) > 1
         calls = res["tredCalls"]
         assert calls["readLen"] == 150
         for l, u, r in zip(loci, units, direct):
@@ -168,7 +177,7 @@ def test_bam_path_equals_packed_path(tmp_path):
             n_called += want["alleles"][0] > 0
             # the simulated short allele is recovered (the long one may exceed what 150 bp reads can size)
         short_ok += sum(calls[l["name"] + ".1"] == int(h) for l, h in zip(loci, h_true[:, 0]))
-    assert n_called == 3 * len(loci)
+    assert n_called == 3 * len(loci) and multi > len(loci)
     assert short_ok >= 0.6 * 3 * len(loci)         # the caller is right on ~80 % of such units (bench.py's check says the same)
     json.dumps(results)          # everything in the results is JSON-serialisable
     engine.close()

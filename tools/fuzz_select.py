@@ -76,6 +76,13 @@ def compare(a, s, pieces, engine):
         if tot_a != tot_b or sorted(map(tuple, ta.tolist())) != sorted(map(tuple, tb.tolist())):
             bad.append("joint")
             break
+        if hb.calls["status"][j] != 0:
+            continue
+        ua, ub = br.joint_units, hb.joint_units
+        sa, sb = slice(ua[3][i0 + j], ua[3][i0 + j] + ua[4][i0 + j]), slice(ub[3][j], ub[3][j] + ub[4][j])
+        if sorted(zip(*(x[sa].tolist() for x in ua[:3]))) != sorted(zip(*(x[sb].tolist() for x in ub[:3]))):
+            bad.append("joint_units")
+            break
     return bad, hi - lo, len(ks)
 
 

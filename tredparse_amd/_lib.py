@@ -214,8 +214,9 @@ class Context:
                 device_id, self.lib.tredgpu_last_error(None).decode()))
         self.h = h
         self.n_ladders = 0
+        self.ladders = None
         self.long_reads = False
-        self._long = None      # the long-read path's ladder table: (ladders, is_long[]) -- see set_ladders
+        self._is_long = None   # the long-read path's mask over self.ladders (None while the path is off) -- see set_ladders
 
     def close(self):
         if getattr(self, "h", None):
@@ -243,18 +244,24 @@ class Context:
         """ladders: list of (prefix, repeat, suffix, max_units).  With the long-read path on (set_long_reads), a ladder
         whose longest template exceeds MAX_TEMPLATE_LEN (up to MAX_LONG_TEMPLATE_LEN) is registered with the library as a
         one-letter stand-in, and every read of it goes to the long kernel."""
+        ladders = list(ladders)
+        native, is_long = ladders, None
         if self.long_reads:
-            return self._set_ladders_long(ladders)
-        self._set_ladders_native(ladders)
-
-    def _set_ladders_native(self, ladders):
-        n = len(ladders)
-        arr = lambda k: (C.c_char_p * max(n, 1))(*[l[k].encode() for l in ladders])
-        mu = np.asarray([l[3] for l in ladders] or [0], np.int32)
+            for i, l in enumerate(ladders):
+                T = self._template_len(l)
+                if T > MAX_LONG_TEMPLATE_LEN:
+                    raise TredGpuError("tredgpu_set_ladders failed: ladder {}: longest template {} exceeds "
+                                       "TREDGPU_MAX_LONG_TEMPLATE_LEN={}".format(i, T, MAX_LONG_TEMPLATE_LEN))
+            is_long = np.array([self._template_len(l) > MAX_TEMPLATE_LEN for l in ladders], bool)
+            # the library's table: a plain one-letter reference stands in for a long ladder (none of its reads reaches it)
+            native = [("N", "A", "", 0) if lg else l for l, lg in zip(ladders, is_long)]
+        n = len(native)
+        arr = lambda k: (C.c_char_p * max(n, 1))(*[l[k].encode() for l in native])
+        mu = np.asarray([l[3] for l in native] or [0], np.int32)
         self._chk(self.lib.tredgpu_set_ladders(self.h, n, arr(0), arr(1), arr(2), mu.ctypes.data),
                   "tredgpu_set_ladders")
         self.n_ladders = n
-        self.ladders = list(ladders)
+        self.ladders, self._is_long = ladders, is_long
 
     # ---- the long-read path (include/tredlong.h) -------------------------------------------------------------
     def set_long_reads(self, enabled):
@@ -264,47 +271,26 @@ class Context:
         tredlong_sw_classify; every other read goes to the library's calls exactly as with the path off.  Refused
         while a registered ladder is longer than MAX_TEMPLATE_LEN and the path is switched off."""
         enabled = bool(enabled)
-        if not enabled and self._long is not None and any(self._long[1]):
+        if not enabled and self._is_long is not None and self._is_long.any():
             raise TredGpuError("a registered ladder is longer than {} columns: register shorter ladders before switching "
                                "the long-read path off".format(MAX_TEMPLATE_LEN))
-        if enabled and not self.long_reads and getattr(self, "ladders", None) is not None:
-            self.long_reads = True
-            self._set_ladders_long(self.ladders)
-        self.long_reads = enabled
+        was, self.long_reads = self.long_reads, enabled
+        if enabled and not was and self.ladders is not None:
+            self.set_ladders(self.ladders)
         if not enabled:
-            self._long = None
+            self._is_long = None
 
     @staticmethod
     def _template_len(l):
         prefix, repeat, suffix, mu = l
         return len(prefix) + len(suffix) + len(repeat) * int(mu) if int(mu) > 0 else len(prefix)
 
-    def _set_ladders_long(self, ladders):
-        ladders = [tuple(l) for l in ladders]
-        for i, l in enumerate(ladders):
-            T = self._template_len(l)
-            if T > MAX_LONG_TEMPLATE_LEN:
-                raise TredGpuError("tredgpu_set_ladders failed: ladder {}: longest template {} exceeds "
-                                   "TREDGPU_MAX_LONG_TEMPLATE_LEN={}".format(i, T, MAX_LONG_TEMPLATE_LEN))
-        is_long = np.array([self._template_len(l) > MAX_TEMPLATE_LEN for l in ladders] or [False], bool)[:len(ladders)]
-        # the library's table: a plain one-letter reference stands in for a long ladder (none of its reads reaches it)
-        self._set_ladders_native([("N", "A", "", 0) if lg else l for l, lg in zip(ladders, is_long)])
-        self.ladders = list(ladders)
-        self._long = (list(ladders), is_long)
-
-    def _check_hist_stride(self, hist_stride, ladder_ids):
-        """The library's hist_stride check against the ladders in full (it only knows the stand-ins of long ones)."""
-        for i in sorted(set(int(k) for k in ladder_ids)):
-            mu = int(self._long[0][i][3])
-            if hist_stride <= mu:
-                raise TredGpuError("hist_stride {} must exceed the max_units {} of ladder {}".format(hist_stride, mu, i))
-
     def _routed_call(self, mem, read_len, n_reads, unit_read_off, unit_ladder, n_units):
         """Reads of a call that take the long path (None: none, the call is the library's own)."""
-        if not self.long_reads or self._long is None or n_reads == 0:
+        if self._is_long is None or n_reads == 0:
             return None
         if mem != MEM_HOST:
-            if any(self._long[1]):
+            if self._is_long.any():
                 raise TredGpuError("the long-read path takes host-memory calls (MEM_HOST) only")
             return None
         rl = np.asarray(read_len)[:n_reads]
@@ -314,9 +300,9 @@ class Context:
         if longest > MAX_LONG_READ_LEN:
             raise TredGpuError("tredgpu_sw_classify failed: read of {} bp exceeds TREDGPU_MAX_LONG_READ_LEN={}".format(
                 longest, MAX_LONG_READ_LEN))
-        if lad.size and (lad.min() < 0 or lad.max() >= len(self._long[1])):
+        if lad.size and (lad.min() < 0 or lad.max() >= len(self._is_long)):
             return None                                   # (the library refuses the call with its own message)
-        routed = (rl > MAX_READ_LEN) | (self._long[1][lad] if lad.size else False)
+        routed = (rl > MAX_READ_LEN) | (self._is_long[lad] if lad.size else False)
         return np.nonzero(routed)[0] if routed.any() else None
 
     def _classify_routed(self, routed, packed, read_off, read_len, unit_read_off, unit_ladder, n_units, params, out_tag,
@@ -339,7 +325,7 @@ class Context:
         sub = np.ascontiguousarray(np.concatenate([pk[woff[r]:woff[r + 1]] for r in routed]), np.uint32)
         uro = np.asarray(unit_read_off)[:n_units + 1].astype(np.int64)
         lad = np.ascontiguousarray(np.repeat(np.asarray(unit_ladder)[:n_units], np.diff(uro))[routed], np.int32)
-        ladders = self._long[0]
+        ladders = self.ladders
         n_l = len(ladders)
         arr = lambda k: (C.c_char_p * n_l)(*[l[k].encode() for l in ladders])
         mu = np.asarray([l[3] for l in ladders], np.int32)
@@ -409,14 +395,10 @@ class Context:
                        calls):
         routed = self._routed_call(mem, read_len, n_reads, unit_read_off, unit_ladder, n_units)
         if routed is not None:
-            # the composition tredgpu_genotype_batch makes of its three host-memory calls, with the long path in the first
-            self._check_hist_stride(hist_stride, range(len(self._long[0])))
-            self._classify_routed(routed, packed, read_off, read_len, unit_read_off, unit_ladder, n_units, params, out_tag,
-                                  out_h, out_score, n_reads=n_reads)
-            self.tally(MEM_HOST, out_tag, out_h, n_reads, unit_read_off, n_units, read_pair_id, hist_stride, full_cnt,
-                       pref_cnt, rept_cnt)
-            return self.likelihood_grid(MEM_HOST, units, n_units, hist_stride, full_cnt, pref_cnt, rept_cnt, global_lens,
-                                        n_global_total, target_lens, n_target_total, calls)
+            return self._genotype_routed(routed, True, self.likelihood_grid, (), packed, read_off, read_len, n_reads,
+                                         unit_read_off, unit_ladder, units, n_units, params, read_pair_id, global_lens,
+                                         n_global_total, target_lens, n_target_total, out_tag, out_h, out_score, hist_stride,
+                                         full_cnt, pref_cnt, rept_cnt, calls)
         self._chk(self.lib.tredgpu_genotype_batch(self.h, mem, _ptr(packed), _ptr(read_off), _ptr(read_len),
                                                   n_reads, _ptr(unit_read_off), _ptr(unit_ladder), _ptr(units),
                                                   n_units, C.byref(params), _ptr(read_pair_id),
@@ -432,17 +414,11 @@ class Context:
         one wait."""
         routed = self._routed_call(MEM_HOST, read_len, n_reads, unit_read_off, unit_ladder, n_units)
         if routed is not None:
-            # SW (the long path included) -> tally -> grid as three host-memory calls
-            self._check_hist_stride(hist_stride, np.asarray(unit_ladder)[:n_units])
-            self._classify_routed(routed, packed, read_off, read_len, unit_read_off, unit_ladder, n_units, params, out_tag,
-                                  out_h, out_score, n_reads=n_reads)
-            full = np.zeros(n_units * hist_stride, np.int32)
-            pref = np.zeros(n_units * hist_stride, np.int32)
-            self.tally(MEM_HOST, out_tag, out_h, n_reads, unit_read_off, n_units, read_pair_id, hist_stride, full, pref,
-                       rept_cnt)
-            return self.likelihood_grid_joint(MEM_HOST, units, n_units, hist_stride, full, pref, rept_cnt, global_lens,
-                                              n_global_total, target_lens, n_target_total, calls, marg, marg_stride,
-                                              joint_off, joint, joint_n, joint_total)
+            return self._genotype_routed(routed, False, self.likelihood_grid_joint,
+                                         (marg, marg_stride, joint_off, joint, joint_n, joint_total), packed, read_off, read_len,
+                                         n_reads, unit_read_off, unit_ladder, units, n_units, params, read_pair_id, global_lens,
+                                         n_global_total, target_lens, n_target_total, out_tag, out_h, out_score, hist_stride,
+                                         None, None, rept_cnt, calls)
         self._chk(self.lib.tredgpu_genotype_batch_joint(self.h, _ptr(packed), _ptr(read_off), _ptr(read_len), n_reads,
                                                         _ptr(unit_read_off), _ptr(unit_ladder), _ptr(units), n_units,
                                                         C.byref(params), _ptr(read_pair_id), _ptr(global_lens), n_global_total,
@@ -450,6 +426,29 @@ class Context:
                                                         _ptr(out_score), hist_stride, _ptr(rept_cnt), _ptr(calls), _ptr(marg),
                                                         marg_stride, _ptr(joint_off), _ptr(joint), _ptr(joint_n),
                                                         _ptr(joint_total)), "tredgpu_genotype_batch_joint")
+
+    def _genotype_routed(self, routed, every_ladder, grid, grid_tail, packed, read_off, read_len, n_reads, unit_read_off,
+                         unit_ladder, units, n_units, params, read_pair_id, global_lens, n_global_total, target_lens,
+                         n_target_total, out_tag, out_h, out_score, hist_stride, full_cnt, pref_cnt, rept_cnt, calls):
+        """genotype_batch / genotype_batch_joint with routed reads: SW (the long path included) -> tally -> grid as host-memory
+        calls, the composition the library makes of them.  grid: likelihood_grid or likelihood_grid_joint, grid_tail its
+        arguments after `calls`; full_cnt / pref_cnt None: histograms of the call's own.  The library only knows the
+        stand-ins of long ladders, so hist_stride is checked here against the ladders in full: every_ladder, against every
+        registered one (tredgpu_genotype_batch checks c->max_ladder_units), else against the batch's own (the fused call
+        checks it per unit)."""
+        ids = range(len(self.ladders)) if every_ladder else np.asarray(unit_ladder)[:n_units]
+        for i in sorted(set(int(k) for k in ids)):
+            mu = int(self.ladders[i][3])
+            if hist_stride <= mu:
+                raise TredGpuError("hist_stride {} must exceed the max_units {} of ladder {}".format(hist_stride, mu, i))
+        self._classify_routed(routed, packed, read_off, read_len, unit_read_off, unit_ladder, n_units, params, out_tag,
+                              out_h, out_score, n_reads=n_reads)
+        if full_cnt is None:
+            full_cnt, pref_cnt = np.zeros(n_units * hist_stride, np.int32), np.zeros(n_units * hist_stride, np.int32)
+        self.tally(MEM_HOST, out_tag, out_h, n_reads, unit_read_off, n_units, read_pair_id, hist_stride, full_cnt, pref_cnt,
+                   rept_cnt)
+        return grid(MEM_HOST, units, n_units, hist_stride, full_cnt, pref_cnt, rept_cnt, global_lens, n_global_total,
+                    target_lens, n_target_total, calls, *grid_tail)
 
     def genotype_selected(self, segs, unit_read_off, unit_word_off, unit_seq4_off, unit_name_off, unit_ladder, units, n_units, params,
                           global_lens, n_global_total, target_lens, n_target_total, out_tag, out_h, out_score, hist_stride, rept_cnt,

@@ -72,7 +72,7 @@ class PackedUnits(object):
             if not len(ks):
                 continue
             ks = np.asarray(ks, np.int64)
-            st, u = _static(scan), scan.unit[ks]
+            u = scan.unit[ks]
             first, n = u["read_first"].astype(np.int64), u["n_reads"].astype(np.int64)
             reads = _ranges(first, n)                         # pool indices of the units' reads, unit after unit
             if isinstance(reads, slice):
@@ -92,21 +92,11 @@ class PackedUnits(object):
             g, t = u["n_global"].astype(np.int64), u["n_target"].astype(np.int64)
             gls.append(scan.global_lens[_ranges(u["global_first"].astype(np.int64), g)])
             tls.append(scan.target_lens[_ranges(u["target_first"].astype(np.int64), t)])
-            r = np.zeros(len(ks), _lib.UNIT_DTYPE)
-            r["period"], r["readlen"], r["ploidy"] = st["period"][ks], scan.readlen, scan.ploidy[ks]
-            r["maxinsert"], r["fullsearch"] = maxinsert, int(fullsearch)
-            r["ref_len"], r["minpe"] = st["span"][ks] + 1, st["span"][ks] + 20
-            r["cutoff_risk"], r["is_expansion"], r["is_recessive"] = st["cutoff_risk"][ks], st["is_expansion"][ks], st["is_recessive"][ks]
-            r["pe_off"], r["n_global"] = n_gl + np.cumsum(g) - g, g
-            r["tl_off"], r["n_target"] = n_tl + np.cumsum(t) - t, t
-            r["half_depth"] = np.asarray(scan.depth, np.float64)[ks] / 2
-            rows.append(r)
+            rows.append(_unit_rows(scan, ks, maxinsert, fullsearch, n_gl + np.cumsum(g) - g, n_tl + np.cumsum(t) - t))
             counts.append(n)
             n_gl += int(g.sum())
             n_tl += int(t.sum())
-            keys = st["ladder"].get(scan.readlen)
-            if keys is None:
-                keys = st["ladder"][scan.readlen] = [(x.prefix, x.repeat, x.suffix, -(-scan.readlen // len(x.repeat))) for x in scan.loci]
+            keys = _ladder_keys(scan)
             b.ladder_keys += [keys[k] for k in ks.tolist()]
         cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts), dt) if parts else np.zeros(0, dt)
         b.params = cat(rows, _lib.UNIT_DTYPE)
@@ -161,6 +151,63 @@ def _static(scan):
 
 
 _STATIC = {}
+
+
+def _ladder_keys(scan):
+    """The template-ladder key (prefix, repeat, suffix, max_units) of every locus of a scan at its read length."""
+    st = _static(scan)
+    keys = st["ladder"].get(scan.readlen)
+    if keys is None:
+        keys = st["ladder"][scan.readlen] = [(x.prefix, x.repeat, x.suffix, -(-scan.readlen // len(x.repeat))) for x in scan.loci]
+    return keys
+
+
+def _unit_rows(scan, ks, maxinsert, fullsearch, pe_off, tl_off):
+    """The grid inputs (UNIT_DTYPE rows) of a scan's loci ks; pe_off / tl_off: where each unit's pair lengths start in the
+    call's global_lens / target_lens."""
+    st, u = _static(scan), scan.unit[ks]
+    r = np.zeros(len(ks), _lib.UNIT_DTYPE)
+    r["period"], r["readlen"], r["ploidy"] = st["period"][ks], scan.readlen, scan.ploidy[ks]
+    r["maxinsert"], r["fullsearch"] = maxinsert, int(fullsearch)
+    r["ref_len"], r["minpe"] = st["span"][ks] + 1, st["span"][ks] + 20
+    r["cutoff_risk"], r["is_expansion"], r["is_recessive"] = st["cutoff_risk"][ks], st["is_expansion"][ks], st["is_recessive"][ks]
+    r["pe_off"], r["n_global"] = pe_off, u["n_global"]
+    r["tl_off"], r["n_target"] = tl_off, u["n_target"]
+    r["half_depth"] = np.asarray(scan.depth, np.float64)[ks] / 2
+    return r
+
+
+def _pad(lens):
+    """A length array as the C ABI takes it: never empty (the count is passed on its own)."""
+    return lens if len(lens) else np.zeros(1, np.int32)
+
+
+def _marg_stride(params, hs):
+    return max(int(params["maxinsert"].max()) if len(params) else 0, hs) + 2
+
+
+def _joint_readback(g, period, call):
+    """The sparse joint distribution of g units: call(joff, trip, jn, jt) makes the library call into room for
+    JOINT_CAP entries per unit; a unit whose flat likelihood surface needs more is asked again with room for every
+    entry.  Returns joint -- per unit (triples {h1, h2, exp(ml - max)}, total) -- and joint_units, the batch's entries as
+    P_h1h2 prints them (alleles in repeat units, values divided by their unit's total) in one pass over the batch's
+    array: (a, b, value, lo, n), laid out by the final capacity; unit i's entries are [lo[i]:lo[i] + n[i]]."""
+    cap = np.full(g, JOINT_CAP, np.int64)
+    while True:
+        joff = np.zeros(g + 1, np.int64)
+        joff[1:] = np.cumsum(cap)
+        trip = np.zeros((int(joff[-1]), 3), np.float64)
+        jn, jt = np.zeros(g, np.int32), np.zeros(g, np.float64)
+        call(joff, trip, jn, jt)
+        if (jn <= cap).all():
+            break
+        cap = np.maximum(cap, jn)
+    joint = [(trip[joff[i]:joff[i] + jn[i]], float(jt[i])) for i in range(g)]
+    per = np.repeat(np.asarray(period, np.int64), cap)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        units = (trip[:, 0].astype(np.int64) // per, trip[:, 1].astype(np.int64) // per, trip[:, 2] / np.repeat(jt, cap),
+                 joff[:-1], jn)
+    return joint, units
 
 
 class _SelectedBatch(object):
@@ -248,40 +295,15 @@ class Engine(object):
         that path goes through the three separate calls, which hand the histograms back."""
         if dense or b.n_units == 0:
             return self._genotype_packed_stepwise(b, dense)
-        r = BatchResult()
-        r.batch = b
-        r.grid = r.grid_off = None
-        g, n = b.n_units, b.n_reads
-        hs = b.max_units + 2
-        ms = max(int(b.params["maxinsert"].max()), hs) + 2
-        r.tag, r.h, r.score = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int16), np.zeros(max(n, 1), np.int16)
-        r.full = r.pref = None
-        r.rept = np.zeros((g, hs), np.int32)
-        lad = self._register(b.ladder_keys)
-        gl = b.global_lens if len(b.global_lens) else np.zeros(1, np.int32)
-        tl = b.target_lens if len(b.target_lens) else np.zeros(1, np.int32)
+        gl, tl = _pad(b.global_lens), _pad(b.target_lens)
         params = _lib.default_sw_params(clip=b.clip)
-        r.calls = np.zeros(g, _lib.CALL_DTYPE)
-        r.marg = np.zeros((g, 2, ms), np.float64)
-        cap = np.full(g, JOINT_CAP, np.int64)
-        while True:
-            joff = np.zeros(g + 1, np.int64)
-            joff[1:] = np.cumsum(cap)
-            trip = np.zeros((int(joff[-1]), 3), np.float64)
-            jn, jt = np.zeros(g, np.int32), np.zeros(g, np.float64)
-            self.ctx.genotype_batch_joint(b.packed, b.read_off, b.read_len, n, b.unit_read_off, lad, b.params, g, params,
-                                          b.pair_id if n else None, gl, len(b.global_lens), tl, len(b.target_lens),
-                                          r.tag, r.h, r.score, hs, r.rept, r.calls, r.marg, ms, joff, trip, jn, jt)
-            if (jn <= cap).all():
-                break
-            cap = np.maximum(cap, jn)         # a flat likelihood surface: ask again with room for every entry
-        r.tag, r.h, r.score = r.tag[:n], r.h[:n], r.score[:n]
-        r.joint = [(trip[joff[i]:joff[i] + jn[i]], float(jt[i])) for i in range(g)]
-        per = np.repeat(b.params["period"].astype(np.int64), cap)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            r.joint_units = (trip[:, 0].astype(np.int64) // per, trip[:, 1].astype(np.int64) // per, trip[:, 2] / np.repeat(jt, cap),
-                             joff[:-1], jn)
-        return r
+
+        def call(r, lad, hs, ms, joff, trip, jn, jt):
+            self.ctx.genotype_batch_joint(b.packed, b.read_off, b.read_len, b.n_reads, b.unit_read_off, lad, b.params, b.n_units,
+                                          params, b.pair_id if b.n_reads else None, gl, len(b.global_lens), tl,
+                                          len(b.target_lens), r.tag, r.h, r.score, hs, r.rept, r.calls, r.marg, ms, joff, trip,
+                                          jn, jt)
+        return self._fused(b, call)
 
     def genotype_selected(self, scans, maxinsert=300, fullsearch=False, clip=False):
         """genotype_packed for samples whose reads the device selected and still holds (feeder._device_scan: SampleScans with
@@ -289,9 +311,6 @@ class Engine(object):
         tagging -> histograms -> grid, one wait -- which also brings back the selected reads' lengths, 4-bit sequences and
         names; they are filled into the scans (per-sample views), so that the writers find what scan_sample would have
         left there.  Every locus of every scan is a unit, in order.  Returns the BatchResult (units in scan order)."""
-        import ctypes as C
-        r = BatchResult()
-        r.grid = r.grid_off = r.full = r.pref = None
         segs, rows, keys, pools, sels = [], [], [], {}, []
         g_all, t_all, n_gl, n_tl = [], [], 0, 0
         for s in scans:
@@ -308,24 +327,12 @@ class Engine(object):
                 segs[-1][1].append(tasks)
             else:
                 segs.append((dev.inf, [tasks]))
-            st, u = _static(s), s.unit
-            row = np.zeros(n, _lib.UNIT_DTYPE)
-            row["period"], row["readlen"], row["ploidy"] = st["period"], s.readlen, s.ploidy
-            row["maxinsert"], row["fullsearch"] = maxinsert, int(fullsearch)
-            row["ref_len"], row["minpe"] = st["span"] + 1, st["span"] + 20
-            row["cutoff_risk"], row["is_expansion"], row["is_recessive"] = st["cutoff_risk"], st["is_expansion"], st["is_recessive"]
-            row["pe_off"], row["n_global"] = gb + u["global_first"], u["n_global"]
-            row["tl_off"], row["n_target"] = tb + u["target_first"], u["n_target"]
-            row["half_depth"] = np.asarray(s.depth, np.float64) / 2
-            rows.append(row)
+            rows.append(_unit_rows(s, np.arange(n), maxinsert, fullsearch, gb + s.unit["global_first"], tb + s.unit["target_first"]))
             sels.append(sel)
-            k = st["ladder"].get(s.readlen)
-            if k is None:
-                k = st["ladder"][s.readlen] = [(x.prefix, x.repeat, x.suffix, -(-s.readlen // len(x.repeat))) for x in s.loci]
-            keys += k
-        params = np.concatenate(rows)
-        sel = np.concatenate(sels)
-        g = len(params)
+            keys += _ladder_keys(s)
+        b = _SelectedBatch()
+        b.params, sel = np.concatenate(rows), np.concatenate(sels)
+        g = b.n_units = len(b.params)
         uro = np.zeros(g + 1, np.int32)
         uwo, uso, uno = (np.zeros(g + 1, np.int64) for _ in range(3))
         np.cumsum(sel["n_reads"], out=uro[1:])
@@ -333,40 +340,20 @@ class Engine(object):
         np.cumsum(sel["seq4_bytes"], out=uso[1:])
         np.cumsum(sel["name_bytes"], out=uno[1:])
         n = int(uro[-1])
-        b = r.batch = _SelectedBatch()
-        b.unit_read_off, b.n_units, b.n_reads, b.params, b.clip, b.ladder_keys, b.pair_id = uro, g, n, params, bool(clip), keys, None
+        b.unit_read_off, b.n_reads, b.clip, b.ladder_keys, b.pair_id = uro, n, bool(clip), keys, None
         b.max_units = max([k[3] for k in keys] + [1])
-        hs = b.max_units + 2
-        ms = max(int(params["maxinsert"].max()), hs) + 2
-        r.tag, r.h, r.score = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int16), np.zeros(max(n, 1), np.int16)
-        r.rept = np.zeros((g, hs), np.int32)
-        lad = self._register(keys)
-        gl = np.ascontiguousarray(np.concatenate(g_all), np.int32) if n_gl else np.zeros(1, np.int32)
-        tl = np.ascontiguousarray(np.concatenate(t_all), np.int32) if n_tl else np.zeros(1, np.int32)
+        gl = _pad(np.ascontiguousarray(np.concatenate(g_all), np.int32))
+        tl = _pad(np.ascontiguousarray(np.concatenate(t_all), np.int32))
         sw = _lib.default_sw_params(clip=clip, max_read_len=max(int(sel["max_len"].max()), 1))
-        r.calls = np.zeros(g, _lib.CALL_DTYPE)
-        r.marg = np.zeros((g, 2, ms), np.float64)
         read_len = np.zeros(max(n, 1), np.int32)
         s4off, nmoff = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
         seq4, names = np.zeros(max(int(uso[-1]), 1), np.uint8), np.zeros(max(int(uno[-1]), 1), np.uint8)
         seg_arg = [(inf, np.concatenate(t)) for inf, t in segs]
-        cap = np.full(g, JOINT_CAP, np.int64)
-        while True:
-            joff = np.zeros(g + 1, np.int64)
-            joff[1:] = np.cumsum(cap)
-            trip = np.zeros((int(joff[-1]), 3), np.float64)
-            jn, jt = np.zeros(g, np.int32), np.zeros(g, np.float64)
-            self.ctx.genotype_selected(seg_arg, uro, uwo, uso, uno, lad, params, g, sw, gl, n_gl, tl, n_tl, r.tag, r.h, r.score, hs,
-                                       r.rept, r.calls, r.marg, ms, joff, trip, jn, jt, read_len, s4off, seq4, nmoff, names)
-            if (jn <= cap).all():
-                break
-            cap = np.maximum(cap, jn)
-        r.tag, r.h, r.score = r.tag[:n], r.h[:n], r.score[:n]
-        r.joint = [(trip[joff[i]:joff[i] + jn[i]], float(jt[i])) for i in range(g)]
-        per = np.repeat(params["period"].astype(np.int64), cap)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            r.joint_units = (trip[:, 0].astype(np.int64) // per, trip[:, 1].astype(np.int64) // per, trip[:, 2] / np.repeat(jt, cap),
-                             joff[:-1], jn)
+
+        def call(r, lad, hs, ms, joff, trip, jn, jt):
+            self.ctx.genotype_selected(seg_arg, uro, uwo, uso, uno, lad, b.params, g, sw, gl, n_gl, tl, n_tl, r.tag, r.h, r.score,
+                                       hs, r.rept, r.calls, r.marg, ms, joff, trip, jn, jt, read_len, s4off, seq4, nmoff, names)
+        r = self._fused(b, call)
         # the reads' arrays, a sample at a time, as scan_sample leaves them (offsets from the sample's first read)
         u0 = 0
         for s in scans:
@@ -381,6 +368,24 @@ class Engine(object):
             u0 += m
         return r
 
+    def _fused(self, b, call):
+        """The BatchResult of a fused call (genotype_packed, genotype_selected) over batch b: its output arrays, the
+        batch's ladders registered, call(r, ladder ids, hist_stride, marg_stride, joff, trip, jn, jt) once per attempt of
+        the joint read-back, the per-read outputs trimmed to the batch's reads."""
+        r = BatchResult()
+        r.batch, r.grid, r.grid_off, r.full, r.pref = b, None, None, None, None
+        g, n = b.n_units, b.n_reads
+        hs = b.max_units + 2
+        ms = _marg_stride(b.params, hs)
+        r.tag, r.h, r.score = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int16), np.zeros(max(n, 1), np.int16)
+        r.rept = np.zeros((g, hs), np.int32)
+        r.calls = np.zeros(g, _lib.CALL_DTYPE)
+        r.marg = np.zeros((g, 2, ms), np.float64)
+        lad = self._register(b.ladder_keys)
+        r.joint, r.joint_units = _joint_readback(g, b.params["period"], lambda *j: call(r, lad, hs, ms, *j))
+        r.tag, r.h, r.score = r.tag[:n], r.h[:n], r.score[:n]
+        return r
+
     def _genotype_packed_stepwise(self, b, dense=False):
         """genotype_packed through the three separate calls (SW, tally, grid)."""
         r = BatchResult()
@@ -392,50 +397,35 @@ class Engine(object):
         r.full, r.pref, r.rept = (np.zeros((g, hs), np.int32) for _ in range(3))
         self.ctx.tally(_lib.MEM_HOST, r.tag if n else np.zeros(1, np.uint8), r.h if n else np.zeros(1, np.int16), n,
                        b.unit_read_off, g, b.pair_id if n else None, hs, r.full, r.pref, r.rept)
-        ms = max(int(b.params["maxinsert"].max()) if g else 0, hs) + 2
-        r.calls, r.marg, r.joint, r.joint_units = self._grid_arrays(b.params, hs, r.full, r.pref, r.rept, b.global_lens,
-                                                                     b.target_lens, ms, units_form=True)
+        hist = (b.params, hs, r.full, r.pref, r.rept, b.global_lens, b.target_lens)
+        r.calls, r.marg, r.joint, r.joint_units = self._grid_arrays(*hist)
         if dense and g:
-            gl = b.global_lens if len(b.global_lens) else np.zeros(1, np.int32)
-            tl = b.target_lens if len(b.target_lens) else np.zeros(1, np.int32)
-            r.grid_off = np.zeros(g + 1, np.int64)
-            r.grid_off[1:] = np.cumsum(np.maximum(r.calls["n_pairs"], 1))
-            r.grid = np.zeros((int(r.grid_off[-1]), 6), np.float64)
-            again = np.zeros(g, _lib.CALL_DTYPE)
-            self.ctx.likelihood_grid(_lib.MEM_HOST, b.params, g, hs, r.full, r.pref, r.rept, gl, len(b.global_lens), tl,
-                                     len(b.target_lens), again, r.grid_off, r.grid, None, 0)
+            r.grid, r.grid_off = self._dense_dump(*hist, r.calls)
         return r
 
-    def _grid_arrays(self, up, hs, full, pref, rept, gl, tl, ms, units_form=False):
-        """likelihood_grid_joint over array inputs; grows the joint capacity when a flat surface needs it.
-        units_form: also the joint entries of the whole batch as P_h1h2 prints them -- alleles in repeat units, values
-        divided by their unit's total -- computed in one pass over the batch's array (a unit's share is three slices;
-        per unit the same arithmetic was thirty small numpy calls per sample)."""
+    def _grid_arrays(self, up, hs, full, pref, rept, gl, tl, joint=True):
+        """The grid of units `up` from their histograms: (calls, marginals, joint, joint_units) -- with joint=False one
+        likelihood_grid call and no joint distribution (None, None)."""
         g = len(up)
-        ngl, ntl = len(gl), len(tl)
-        gl = gl if ngl else np.zeros(1, np.int32)
-        tl = tl if ntl else np.zeros(1, np.int32)
+        ms = _marg_stride(up, hs)
         calls = np.zeros(g, _lib.CALL_DTYPE)
         marg = np.zeros((g, 2, ms), np.float64)
-        cap = np.full(g, JOINT_CAP, np.int64)
-        while True:
-            joff = np.zeros(g + 1, np.int64)
-            joff[1:] = np.cumsum(cap)
-            trip = np.zeros((int(joff[-1]), 3), np.float64)
-            jn, jt = np.zeros(g, np.int32), np.zeros(g, np.float64)
-            self.ctx.likelihood_grid_joint(_lib.MEM_HOST, up, g, hs, full, pref, rept, gl, ngl, tl, ntl, calls, marg, ms,
-                                           joff, trip, jn, jt)
-            if (jn <= cap).all():
-                break
-            cap = np.maximum(cap, jn)
-        joint = [(trip[joff[i]:joff[i] + jn[i]], float(jt[i])) for i in range(g)]
-        if not units_form:
-            return calls, marg, joint
-        per = np.repeat(up["period"].astype(np.int64), cap)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            ju = (trip[:, 0].astype(np.int64) // per, trip[:, 1].astype(np.int64) // per, trip[:, 2] / np.repeat(jt, cap),
-                  joff[:-1], jn)
-        return calls, marg, joint, ju
+        grid = (_lib.MEM_HOST, up, g, hs, full, pref, rept, _pad(gl), len(gl), _pad(tl), len(tl), calls)
+        if not joint:
+            self.ctx.likelihood_grid(*grid, None, None, marg, ms)
+            return calls, marg, None, None
+        return (calls, marg) + _joint_readback(g, up["period"], lambda *j: self.ctx.likelihood_grid_joint(*grid, marg, ms, *j))
+
+    def _dense_dump(self, up, hs, full, pref, rept, gl, tl, calls):
+        """The four terms of every (h1, h2) pair of the units' grids ({h1, h2, ml1..ml4} per pair, unit i's pairs from
+        grid_off[i]): a second likelihood_grid call, with the dump."""
+        g = len(up)
+        grid_off = np.zeros(g + 1, np.int64)
+        grid_off[1:] = np.cumsum(np.maximum(calls["n_pairs"], 1))
+        grid = np.zeros((int(grid_off[-1]), 6), np.float64)
+        self.ctx.likelihood_grid(_lib.MEM_HOST, up, g, hs, full, pref, rept, _pad(gl), len(gl), _pad(tl), len(tl),
+                                 np.zeros(g, _lib.CALL_DTYPE), grid_off, grid, None, 0)
+        return grid, grid_off
 
     # ---- (1) SW + tagging only -----------------------------------------------------------------------
     def classify(self, units, want_dump=False):
@@ -507,8 +497,7 @@ class Engine(object):
     def _grid(self, units, hs, full, pref, rept, want_grid, dense=False):
         """One grid call for the batch.  want_grid: also the joint distribution -- sparse (triples + total per
         unit, tredgpu_likelihood_grid_joint) unless dense=True asks for the full dump of every pair."""
-        g = len(units)
-        up = np.zeros(g, _lib.UNIT_DTYPE)
+        up = np.zeros(len(units), _lib.UNIT_DTYPE)
         gl, tl = [], []
         for i, u in enumerate(units):
             t = u.tred
@@ -517,37 +506,9 @@ class Engine(object):
                      len(tl), len(u.target_lens), u.depth / 2)
             gl += u.global_lens
             tl += u.target_lens
-        ngl, ntl = len(gl), len(tl)
-        gl = np.asarray(gl or [0], np.int32)
-        tl = np.asarray(tl or [0], np.int32)
-        calls = np.zeros(g, _lib.CALL_DTYPE)
-        ms = max(max(u.maxinsert for u in units), hs) + 2
-        marg = np.zeros((g, 2, ms), np.float64)
-        dump = goff = joint = None
-        if want_grid and not dense:
-            cap = np.full(g, JOINT_CAP, np.int64)
-            while True:
-                joff = np.zeros(g + 1, np.int64)
-                joff[1:] = np.cumsum(cap)
-                trip = np.zeros((int(joff[-1]), 3), np.float64)
-                jn = np.zeros(g, np.int32)
-                jt = np.zeros(g, np.float64)
-                self.ctx.likelihood_grid_joint(_lib.MEM_HOST, up, g, hs, full, pref, rept, gl, ngl, tl, ntl, calls,
-                                               marg, ms, joff, trip, jn, jt)
-                if (jn <= cap).all():
-                    break
-                cap = np.maximum(cap, jn)     # a flat likelihood surface: ask again with room for every entry
-            joint = [(trip[joff[i]:joff[i] + jn[i]], float(jt[i])) for i in range(g)]
-        else:
-            self.ctx.likelihood_grid(_lib.MEM_HOST, up, g, hs, full, pref, rept, gl, ngl, tl, ntl, calls, None, None,
-                                     marg, ms)
-        if want_grid and dense:
-            goff = np.zeros(g + 1, np.int64)
-            goff[1:] = np.cumsum(np.maximum(calls["n_pairs"], 1))
-            dump = np.zeros((int(goff[-1]), 6), np.float64)
-            calls2 = np.zeros(g, _lib.CALL_DTYPE)
-            self.ctx.likelihood_grid(_lib.MEM_HOST, up, g, hs, full, pref, rept, gl, ngl, tl, ntl, calls2, goff, dump,
-                                     None, 0)
+        hist = (up, hs, full, pref, rept, np.asarray(gl, np.int32), np.asarray(tl, np.int32))
+        calls, marg, joint, _ = self._grid_arrays(*hist, joint=want_grid and not dense)
+        dump, goff = self._dense_dump(*hist, calls) if want_grid and dense else (None, None)
         return calls, marg, dump, goff, joint
 
     def grid_from_counts(self, unit, full, pref, rept):
