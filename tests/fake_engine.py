@@ -56,7 +56,7 @@ class FakeEngine(object):
         b = eng._SelectedBatch()
         rows, counts = [], []
         for s in scans:
-            dev, t0, sel = s.device
+            dev, t0, sel = s.device.chunk, s.device.first_task, s.device.sel
             lens, seqs, names = [], [], []
             for k in range(len(s.names)):
                 a, q, nm = dev.inf.selected_reads(t0 + k)

@@ -295,3 +295,171 @@ def test_a_failed_call_over_device_selected_reads_falls_back_to_the_host_scan(co
         for k, v in w["tredCalls"].items():
             if k.endswith((".DP", ".PEDP", ".PEG", ".PET")) or k in ("depthY", "readLen"):
                 assert g["tredCalls"][k] == v, k
+
+
+# ---- the feeder when its consumer stops half way (gpu_walk + gpu_select) ------------------------------------------------
+GUARD = 20       # seconds: only tells "returns" from "hangs" (the feeder's own polls are 0.1 s)
+
+
+class _CountingInflater(ModelInflater):
+    closed = []
+
+    def close(self):
+        _CountingInflater.closed.append(self)
+
+
+class _CountedHandle(object):
+    """A BAM handle whose close() calls are counted; everything else is the handle's own."""
+    def __init__(self, f):
+        self.__dict__.update(f=f, closed=0)
+
+    def __getattr__(self, key):
+        return getattr(self.f, key)
+
+    def close(self):
+        self.closed += 1
+        return self.f.close()
+
+
+@pytest.fixture
+def stand_ins(monkeypatch):
+    """ModelInflater (its close() calls counted) in the inflater's place and every handle that bam_parser.open_bam gives out
+    -- the feeder's plans and the host's scans open theirs there -- recorded.  Returns that list."""
+    from tredparse_amd import bam_parser
+    if not hasattr(bamio.AlignmentFile(os.path.join(GOLD, "bam", "t001.bam")), "plan_walks"):
+        pytest.skip("no native BAM layer")
+    handles, real = [], bam_parser.open_bam
+
+    def open_counted(path):
+        handles.append(_CountedHandle(real(path)))
+        return handles[-1]
+    monkeypatch.setattr(bam_parser, "open_bam", open_counted)
+    monkeypatch.setattr("tredparse_amd._lib.Inflater", _CountingInflater)
+    t.release_inflaters()                                       # (none of another test's in the process's pool)
+    del ModelInflater.made[:], _CountingInflater.closed[:]
+    yield handles
+    t.release_inflaters()
+
+
+def _small_cohort(n=16):
+    repo = TREDsRepo(ref="hg38", sites=os.path.join(GOLD, "no_sites"))
+    return [("s{:02d}".format(i), os.path.join(GOLD, "bam", ("t001", "t002")[i % 2] + ".bam"), repo, ["HD", "DM1"], 300, False, False, True,
+             True, "ERROR") for i in range(n)]
+
+
+def _decoded_chunks():
+    return sum(m.walks for m in ModelInflater.made)
+
+
+def _wait_until(cond, seconds=10):
+    import time
+    deadline = time.time() + seconds
+    while not cond() and time.time() < deadline:
+        time.sleep(0.02)
+    return cond()
+
+
+def _all_is_given_back(handles, threads_before):
+    """After a feeder has ended, however: its three inflaters are in the process's pool and none was closed, its threads
+    are gone, and every handle that was opened has been closed exactly once."""
+    import threading
+    from tredparse_amd import feeder
+    pooled = [inf for v in feeder._INFLATERS.values() for inf in v]
+    assert len(ModelInflater.made) == 3 and sorted(map(id, pooled)) == sorted(map(id, ModelInflater.made))
+    assert _CountingInflater.closed == []
+    assert _wait_until(lambda: threading.active_count() <= threads_before), [th.name for th in threading.enumerate()]
+    assert handles and [h.closed for h in handles] == [1] * len(handles)
+
+
+def test_close_returns_with_device_chunks_the_consumer_never_took(stand_ins):
+    """ADVICE r6, first item: with the selection on the device a slot is refilled only when the consumer has released its
+    chunk (DeviceChunk.done).  A consumer that stops after it has taken a chunk releases nothing more: the feeder, which by
+    then waits for such a release, must still stop when close() tells it to, and give everything back."""
+    import threading
+    tasks = _small_cohort(16)
+    chunks = [tasks[i:i + 2] for i in range(0, 16, 2)]
+    before = threading.active_count()
+    ex = ThreadPoolExecutor(max_workers=2)
+    feeder = t._InflateFeeder(chunks, ex, 0, walk=True, select=True)
+    chunk, futs = feeder.next()
+    scans = [f.result() for f in futs]
+    assert [s.device is not None for s in scans] == [True, True]            # (held: this consumer never releases them)
+    # the feeder runs ahead: chunks 1 and 2 wait in the queue, and chunk 3 needs the first chunk's inflater
+    assert _wait_until(lambda: _decoded_chunks() == 3 and feeder.q.full())
+    th = threading.Thread(target=feeder.close, daemon=True)
+    th.start()
+    th.join(GUARD)
+    assert not th.is_alive(), "close() hangs"
+    ex.shutdown()
+    assert _decoded_chunks() == 3
+    _all_is_given_back(stand_ins, before)
+
+
+@pytest.mark.parametrize("how", ["sink", "emit"])
+def test_run_many_with_the_selection_on_the_device_stops_when_the_consumer_fails(stand_ins, how):
+    """The consumer fails behind genotype_scans -- a sink that raises; a writer's error, which run_many raises behind the
+    chunk's submits -- while the feeder is chunks ahead and waits for a release: the caller sees the consumer's own
+    exception, nothing is left behind, and the next cohort goes through the same pooled inflaters, every sample once."""
+    import threading
+    from tests.fake_engine import FakeEngine
+    tasks = _small_cohort(16)
+    ahead = []
+
+    def fail():
+        # (not before the feeder is as far ahead as it gets: two chunks queued, a third decoded, the next waiting for a slot)
+        ahead.append(_wait_until(lambda: _decoded_chunks() >= 4))
+        return RuntimeError("the consumer failed")
+
+    class FailingEmit(object):
+        error, n = None, 0
+
+        def submit(self, arg, scan, parts):
+            self.n += 1
+            if self.n == 1:
+                self.error = fail()
+    seen = []
+
+    def sink(result):
+        seen.append(result["samplekey"])
+        if len(seen) == 2:
+            raise fail()
+    kw = dict(batch=2, threads=2, lazy_details=True, inflate_device=0, gpu_walk=True, gpu_select=True)
+    kw.update({"sink": sink} if how == "sink" else {"emit": FailingEmit()})
+    caught = []
+
+    def consumer():
+        try:
+            t.run_many(tasks, FakeEngine(seed=3, odd_units=False), **kw)
+        except BaseException as e:
+            caught.append(e)
+    before = threading.active_count()
+    th = threading.Thread(target=consumer, daemon=True)
+    th.start()
+    th.join(GUARD + 10)                                          # (+ the wait inside fail())
+    assert not th.is_alive(), "run_many hangs"
+    assert ahead == [True]
+    assert len(caught) == 1 and isinstance(caught[0], RuntimeError) and str(caught[0]) == "the consumer failed"
+    _all_is_given_back(stand_ins, before)
+    # and the good path: the same cohort through the same three inflaters
+    out = t.run_many(tasks, FakeEngine(seed=3, odd_units=False), batch=2, threads=2, lazy_details=True, inflate_device=0, gpu_walk=True,
+                     gpu_select=True)
+    assert [r["samplekey"] for r in out] == [a[0] for a in tasks]
+    _all_is_given_back(stand_ins, before)
+
+
+def test_a_device_chunk_released_twice_or_late_is_harmless(stand_ins):
+    """DeviceChunk.done() any number of times, and after the feeder that made the chunk has been closed: nothing raises."""
+    ex = ThreadPoolExecutor(max_workers=2)
+    tasks = _small_cohort(4)
+    feeder = t._InflateFeeder([tasks[:2], tasks[2:]], ex, 0, walk=True, select=True)
+    try:
+        lease = [f.result() for f in feeder.next()[1]][0].device.chunk
+        lease.done()
+        lease.done()
+        late = [f.result() for f in feeder.next()[1]][0].device.chunk
+    finally:
+        feeder.close()
+        ex.shutdown()
+    late.done()
+    lease.done()
+    assert late.release.done() and lease.release.done()

@@ -307,14 +307,14 @@ class Engine(object):
 
     def genotype_selected(self, scans, maxinsert=300, fullsearch=False, clip=False):
         """genotype_packed for samples whose reads the device selected and still holds (feeder._device_scan: SampleScans with
-        `.device` = (DeviceChunk, first task, select results)): one tredgpu_genotype_selected call -- pack on the device, SW +
+        `.device` = feeder.DeviceReads: the chunk's lease, the sample's first task, its select results): one tredgpu_genotype_selected call -- pack on the device, SW +
         tagging -> histograms -> grid, one wait -- which also brings back the selected reads' lengths, 4-bit sequences and
         names; they are filled into the scans (per-sample views), so that the writers find what scan_sample would have
         left there.  Every locus of every scan is a unit, in order.  Returns the BatchResult (units in scan order)."""
         segs, rows, keys, pools, sels = [], [], [], {}, []
         g_all, t_all, n_gl, n_tl = [], [], 0, 0
         for s in scans:
-            dev, t0, sel = s.device
+            dev, t0, sel = s.device.chunk, s.device.first_task, s.device.sel
             n = len(s.names)
             if dev not in pools:
                 pools[dev] = (n_gl, n_tl)

@@ -268,18 +268,17 @@ def _genotype(engine, picks, o):
 
 
 def genotype_scans(engine, task_args, scans):
-    from ._lib import TredGpuError
-    return _genotype_scans(engine, task_args, scans, TredGpuError)
-
-
-def _genotype_scans(engine, task_args, scans, TredGpuError):
     """GPU half of a batch: the kernels' results for every unit of the scans, (picks, parts) with parts as _genotype
     returns them (unit_results turns them into per-unit views).
     The kernel-side options of a GPU batch are the batch's: tasks that differ in them go in separate batches (the CLI's
     are uniform; API callers of run_many may mix them)."""
+    from ._lib import TredGpuError
     picks = [(si, s, [k for k in range(len(s.names)) if k not in s.dropped] if s.opened else [])
              for si, s in enumerate(scans)]
     t0 = time.perf_counter()
+    # the leases on the inflaters that hold device-selected reads (feeder.DeviceChunk), taken down before on_the_host
+    # replaces scans: they are given back in ONE place, the finally below, whatever became of their samples
+    leases = set(s.device.chunk for s in scans if getattr(s, "device", None) is not None)
     groups = {}
     for pick, arg in zip(picks, task_args):
         o = _options(arg)
@@ -298,7 +297,6 @@ def _genotype_scans(engine, task_args, scans, TredGpuError):
             scans[si] = h
             picks[si] = (si, h, [k for k in range(len(h.names)) if k not in h.dropped] if h.opened else [])
             again.append(picks[si])
-            s.device[0].done()
         parts.update(_genotype(engine, again, o))
     try:
         for key, (o, sub) in groups.items():
@@ -320,10 +318,8 @@ def _genotype_scans(engine, task_args, scans, TredGpuError):
             if odd:
                 on_the_host(o, odd)
     finally:
-        for _, s, _ in picks:                  # the inflaters that held the device's selections are the feeder's again
-            dev = getattr(s, "device", None)
-            if dev is not None:
-                dev[0].done()
+        for lease in leases:                   # the inflaters that held the device's selections are the feeder's again
+            lease.done()
     timing_add(gpu=time.perf_counter() - t0, gpu_calls=len(groups))
     return picks, parts
 
