@@ -56,6 +56,11 @@ assert CALL_DTYPE.itemsize == C.sizeof(Call) == 56
 # the long-read path's symbols (include/tredlong.h)
 LONG_EXPORTS = ("tredlong_sw_classify", "tredlong_last_error")
 
+# the CIGAR kernel's symbols (include/tredcigar.h)
+CIGAR_EXPORTS = ("tredcigar_sw_cigar", "tredcigar_get_timing", "tredcigar_reset_timing", "tredcigar_release",
+                 "tredcigar_last_error")
+CIGAR_OK, CIGAR_NO_PATH, CIGAR_OFF_EDGE, CIGAR_OVERFLOW, CIGAR_TOO_LONG, CIGAR_BAD_ITEM = 0, 1, 2, 3, 4, 5
+
 # every symbol include/tredgpu.h declares (tests check the .so exports them all)
 EXPORTS = ("tredgpu_create", "tredgpu_destroy", "tredgpu_last_error", "tredgpu_sync", "tredgpu_get_stream",
            "tredgpu_version", "tredgpu_set_ladders", "tredgpu_set_model", "tredgpu_pack_reads",
@@ -90,6 +95,14 @@ def load():
                                              C.POINTER(C.c_char_p), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, C.c_int32]
     lib.tredlong_last_error.argtypes = []
     lib.tredlong_last_error.restype = C.c_char_p
+    lib.tredcigar_sw_cigar.argtypes = [vp, C.c_int, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                       vp, vp, vp, vp, i64, vp, vp, vp, C.POINTER(SwParams), i32, vp, vp, vp]
+    lib.tredcigar_get_timing.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
+    lib.tredcigar_reset_timing.argtypes = [vp]
+    lib.tredcigar_release.argtypes = [vp]
+    lib.tredcigar_release.restype = None
+    lib.tredcigar_last_error.argtypes = []
+    lib.tredcigar_last_error.restype = C.c_char_p
     lib.tredgpu_get_stream.argtypes = [vp]
     lib.tredgpu_get_stream.restype = vp
     lib.tredgpu_version.restype = C.c_char_p
@@ -220,6 +233,7 @@ class Context:
 
     def close(self):
         if getattr(self, "h", None):
+            self.lib.tredcigar_release(self.h)
             self.lib.tredgpu_destroy(self.h)
             self.h = None
 
@@ -469,12 +483,36 @@ class Context:
                                                      _ptr(read_len), _ptr(seq4_off), _ptr(seq4), _ptr(name_off), _ptr(names)),
                   "tredgpu_genotype_selected")
 
+    def sw_cigar(self, mem, packed, read_off, read_len, n_items, item_ladder, item_template, fields, params, cap, out_ops,
+                 out_n_ops, out_status, ladders=None):
+        """tredcigar_sw_cigar (include/tredcigar.h): the reference's CIGAR of n_items alignments.  Item k is read k
+        (packed / read_off / read_len as pack_reads writes them) against template item_template[k] (db order) of ladder
+        item_ladder[k], placed by fields[k] = {score, ref_begin, ref_end, read_begin, read_end} (int16 [n][5]: a row of
+        sw_classify's dump).  out_ops: uint32 [n][cap] (length << 4 | op, M=0 I=1 D=2), out_n_ops / out_status: int32 [n]
+        (CIGAR_*).  ladders: the table the indices refer to (default: the one registered with set_ladders)."""
+        ladders = list(self.ladders if ladders is None else ladders)
+        n_l = len(ladders)
+        arr = lambda k: (C.c_char_p * max(n_l, 1))(*[l[k].encode() for l in ladders])
+        mu = np.asarray([l[3] for l in ladders] or [0], np.int32)
+        prefixes, repeats, suffixes = arr(0), arr(1), arr(2)
+        rc = self.lib.tredcigar_sw_cigar(self.h, mem, n_l, prefixes, repeats, suffixes, _ptr(mu), _ptr(packed), _ptr(read_off),
+                                         _ptr(read_len), n_items, _ptr(item_ladder), _ptr(item_template), _ptr(fields),
+                                         C.byref(params), cap, _ptr(out_ops), _ptr(out_n_ops), _ptr(out_status))
+        if rc != 0:
+            raise TredGpuError("tredcigar_sw_cigar failed ({}): {}".format(rc, self.lib.tredcigar_last_error().decode()))
+
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")
+        if self.lib.tredcigar_reset_timing(self.h) != 0:
+            raise TredGpuError("tredcigar_reset_timing failed: {}".format(self.lib.tredcigar_last_error().decode()))
 
     def get_timing(self, which):
         """(launches, total device ms) of kernel `which` since reset_timing (HIP events)."""
         n, ms = C.c_int64(0), C.c_double(0)
+        if which == KERNEL_CIGAR:
+            if self.lib.tredcigar_get_timing(self.h, C.byref(n), C.byref(ms)) != 0:
+                raise TredGpuError("tredcigar_get_timing failed: {}".format(self.lib.tredcigar_last_error().decode()))
+            return n.value, ms.value
         self._chk(self.lib.tredgpu_get_timing(self.h, which, C.byref(n), C.byref(ms)), "tredgpu_get_timing")
         return n.value, ms.value
 
@@ -492,6 +530,7 @@ class Context:
 
 KERNEL_SW, KERNEL_TALLY, KERNEL_GRID = 0, 1, 2
 KERNEL_GRID_PREPARE, KERNEL_GRID_PAIRS, KERNEL_GRID_REDUCE, KERNEL_GRID_KDE = 3, 4, 5, 6
+KERNEL_CIGAR = 16               # include/tredcigar.h; tredgpu_get_timing's own series ends at 6
 
 
 def default_sw_params(clip=False, max_read_len=0):

@@ -20,7 +20,7 @@ class Emitter(object):
     natively (libtredbam.so tredbam_emit_sample_files, include/tredbam.h) on `workers` threads that run WITHOUT the
     interpreter lock -- instead of building every sample's tredCalls dict (format_scans) and printing it (to_json,
     to_vcf) in Python, which was what bounded a driver process.  The text is byte for byte the Python path's
-    (tests/test_emit_native.py).  A sample the native printers do not cover -- --log DEBUG, a BAM that did not open, a
+    (tests/test_emit_native.py).  A sample the native printers do not cover -- --log DEBUG, --alignments, a BAM that did not open, a
     batch the retries cut into single units, names outside ASCII -- goes through the Python path on the same thread.
       echo      print each JSON on stdout as to_json does (one worker then: the order of the samples is kept)
       on_sample called with {'samplekey', 'names', 'printed' (bool per locus), 'first_allele' (units, per locus)} after a
@@ -72,9 +72,15 @@ class Emitter(object):
         """The sample through format_scans and the Python writers (what the native path must equal)."""
         from .tred import format_scans, unit_results, write_vcf_json
         picks = [(0, scan, [k for _, _, ks in pieces for k in ks])]
-        result = format_scans([arg], [scan], picks, unit_results({0: pieces}), lazy_details=True)[0]
+        res = unit_results({0: pieces})
+        result = format_scans([arg], [scan], picks, res, lazy_details=True)[0]
         if not self.no_output:
             write_vcf_json(result, self.ref, self.repo, self.treds, quiet=not self.echo)
+            o = _options(arg)
+            if o["alignments"]:
+                from .tred import alignments_text
+                with open(result["samplekey"] + ".alignments.txt", "w") as fp:
+                    fp.write(alignments_text(scan, result["tredCalls"], {k: r for (_, k), r in res.items()}, o["repeatpairs"] or o["clip"]))
         if self.on_sample is not None:
             calls = result["tredCalls"]
             self.on_sample({"samplekey": result["samplekey"], "names": scan.names,
@@ -86,7 +92,7 @@ class Emitter(object):
         import numpy as np
         from . import bamio
         o = _options(arg)
-        native = scan.opened and len(pieces) == 1 and o["log"] != "DEBUG" and getattr(pieces[0][0], "joint_units", None) is not None
+        native = scan.opened and len(pieces) == 1 and o["log"] != "DEBUG" and not o["alignments"] and getattr(pieces[0][0], "joint_units", None) is not None
         table = self._table(scan.names) if native else None
         if table is None or (self.no_output and self.on_sample is None):
             if not (self.no_output and self.on_sample is None and o["log"] != "DEBUG"):

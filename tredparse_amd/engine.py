@@ -218,7 +218,7 @@ class _SelectedBatch(object):
 class BatchResult(object):
     """Arrays of one genotyped PackedUnits batch; unit(i) gives the per-unit view the callers format."""
     __slots__ = ("batch", "tag", "h", "score", "full", "pref", "rept", "calls", "marg", "joint", "grid", "grid_off",
-                 "joint_units", "repeatpairs", "_emit")
+                 "joint_units", "repeatpairs", "_emit", "alignments")
 
     def unit(self, i):
         b = self.batch
@@ -238,6 +238,8 @@ class BatchResult(object):
             a, b, v, lo, n = ju
             r.joint_units = (a[lo[i]:lo[i] + n[i]], b[lo[i]:lo[i] + n[i]], v[lo[i]:lo[i] + n[i]])
         r.P_h1, r.P_h2 = self.marg[i, 0], self.marg[i, 1]
+        al = getattr(self, "alignments", None)
+        r.alignments = al[i] if al is not None else None           # Engine.alignments' entry of the unit (--alignments)
         return r
 
 
@@ -245,7 +247,22 @@ class UnitResult(object):
     """grid: the dense dump {h1, h2, ml1..ml4} per pair (only when asked for); joint: (triples {h1, h2, exp(ml - max)}
     of the pairs >= e^-10, total over all distinct pairs) -- what P_h1h2 is printed from."""
     __slots__ = ("tags", "hs", "scores", "full", "pref", "rept_hist", "rept", "call", "grid", "joint", "P_h1", "P_h2",
-                 "joint_units")
+                 "joint_units", "alignments")
+
+
+class ReadAlignment(object):
+    """How one tagged read was laid on the template it was counted for (Engine.alignments): tag, h (repeat units),
+    strand (0: the template as written, 1: its reverse complement), target (the template's text) and al, the
+    ssw.PyAlignRes of the pair with its CIGAR."""
+    __slots__ = ("tag", "h", "strand", "target", "al")
+
+    def __init__(self, tag, h, strand, target, al):
+        self.tag, self.h, self.strand, self.target, self.al = tag, h, strand, target, al
+
+    def verbose(self):
+        """The reference's verbose block for the pair (bam_parser.py:145-147): `units target`, str(al).strip(), the
+        three lines of al.alignment."""
+        return "\n".join(["{} {}".format(self.h, self.target), str(self.al).strip()] + list(self.al.alignment)) + "\n"
 
 
 class Engine(object):
@@ -460,6 +477,57 @@ class Engine(object):
         if (tag[:n] == _lib.TAG_INVALID).any():
             raise _lib.TredGpuError("a read exceeds TREDGPU_MAX_READ_LEN")
         return tag[:n], h[:n], sc[:n], uro, (dump[:n] if want_dump else None)
+
+    # ---- (1b) the alignment behind every tagged read --------------------------------------------------
+    def alignments(self, units):
+        """Per unit: {read index in the unit: ReadAlignment} for every tagged read (HANG included).  classify with the
+        dump, then per tagged read the winning dump row -- the highest score, then the fewest units, then the first row
+        in db order (bam_parser.py:174), which is the pair out_tag / out_h stand for -- and ONE sw_cigar call for all
+        winners."""
+        from .bam_parser import rc
+        from .ssw import PyAlignRes
+        tag, h, sc, uro, dump = self.classify(units, want_dump=True)
+        out = [{} for _ in units]
+        items = np.nonzero(tag != _lib.TAG_NONE)[0]
+        m = len(items)
+        if m == 0:
+            return out
+        # rows in db order are u=1 fwd, u=1 rc, u=2 fwd, ...: the first row with the highest score has the fewest units
+        rows = dump[items]
+        key = np.where(rows[:, :, 5] > 0, rows[:, :, 0].astype(np.int32), -1)
+        win = key.argmax(axis=1).astype(np.int32)
+        best = rows[np.arange(m), win]
+        assert (best[:, 0] == sc[items]).all() and (best[:, 5] == tag[items]).all() and (win // 2 + 1 == h[items]).all(), \
+            "the winning dump row is not the pair the read was tagged for"
+        unit_of = (np.searchsorted(uro, items, side="right") - 1).astype(np.int64)
+        lad_index = {k: i for i, k in enumerate(self._ladders)}
+        unit_ladder = np.asarray([lad_index[(u.tred.prefix, u.tred.repeat, u.tred.suffix, u.max_units)] for u in units], np.int32)
+        reads = [units[g].reads[i - int(uro[g])] for g, i in zip(unit_of.tolist(), items.tolist())]
+        packed, woff, rlen = _lib.pack_reads(reads)
+        fields = np.ascontiguousarray(best[:, :5], np.int16)
+        clip = bool(units[0].clip)
+        cap = 32
+        while True:
+            ops, n_ops, status = np.zeros((m, cap), np.uint32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+            self.ctx.sw_cigar(_lib.MEM_HOST, packed, woff, rlen, m, np.ascontiguousarray(unit_ladder[unit_of]), win, fields,
+                              _lib.default_sw_params(clip=clip), cap, ops, n_ops, status, ladders=self._ladders)
+            if not (status == _lib.CIGAR_OVERFLOW).any():
+                break
+            cap = int(n_ops.max())            # (a CIGAR of more than 32 operations: once more with the room it needs)
+        if (status != _lib.CIGAR_OK).any():
+            k = int(np.nonzero(status != _lib.CIGAR_OK)[0][0])
+            raise _lib.TredGpuError("sw_cigar: status {} for read {} of unit {}".format(int(status[k]), int(items[k] - uro[unit_of[k]]),
+                                                                                      int(unit_of[k])))
+        targets = {}
+        for j in range(m):
+            g, t = int(unit_of[j]), int(win[j])
+            if (g, t) not in targets:
+                x = units[g].tred
+                text = x.prefix + x.repeat * (t // 2 + 1) + x.suffix
+                targets[(g, t)] = rc(text) if t % 2 else text
+            al = PyAlignRes(best[j], reads[j], targets[(g, t)], ops[j, :n_ops[j]])
+            out[g][int(items[j] - uro[g])] = ReadAlignment(int(tag[items[j]]), int(h[items[j]]), t % 2, targets[(g, t)], al)
+        return out
 
     # ---- the whole path ------------------------------------------------------------------------------
     def genotype(self, units, want_grid=True):

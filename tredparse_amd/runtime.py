@@ -46,10 +46,11 @@ def timeline_dump():
 
 
 def _options(arg):
-    """The reference's run() argument tuple, named."""
-    samplekey, bam, repo, names, maxinsert, fullsearch, clip, alts, repeatpairs, log = arg
+    """The reference's run() argument tuple, named; an eleventh member, where there is one, is --alignments."""
+    samplekey, bam, repo, names, maxinsert, fullsearch, clip, alts, repeatpairs, log = arg[:10]
     return dict(samplekey=samplekey, bam=bam, repo=repo, names=list(names), maxinsert=maxinsert,
-                fullsearch=fullsearch, clip=clip, alts=alts, repeatpairs=repeatpairs, log=log)
+                fullsearch=fullsearch, clip=clip, alts=alts, repeatpairs=repeatpairs, log=log,
+                alignments=bool(arg[10]) if len(arg) > 10 else False)
 
 
 def collect_sample(arg, long_reads=False):

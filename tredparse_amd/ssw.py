@@ -21,10 +21,66 @@ def _context():
 
 
 class PyAlignRes(object):
-    def __init__(self, rec, query_seq, ref_seq):
+    """The reference's result object (ssw_wrap.py:259-383): the five fields, score2 = None, and -- from the operations
+    `ops` (length << 4 | op, M=0 I=1 D=2; empty without report_cigar) -- its cigar_string / cigar, iter_cigar, alignment
+    and str() texts."""
+
+    def __init__(self, rec, query_seq, ref_seq, ops=()):
         self.score, self.ref_begin, self.ref_end, self.query_begin, self.query_end = (int(x) for x in rec[:5])
         self.score2 = None
         self.ref_seq, self.query_seq = ref_seq, query_seq
+        self._cigar_string = [int(v) for v in ops]
+
+    def __str__(self):                                                    # ssw_wrap.py:284-300
+        msg = "OPTIMAL MATCH\n"
+        msg += "Score            {}\n".format(self.score)
+        msg += "Reference begin  {}\n".format(self.ref_begin)
+        msg += "Reference end    {}\n".format(self.ref_end)
+        msg += "Query begin      {}\n".format(self.query_begin)
+        msg += "Query end        {}\n".format(self.query_end)
+        if self.cigar_string:
+            msg += "Cigar_string     {}\n".format(self.cigar_string)
+        return msg
+
+    @property
+    def iter_cigar(self):                                                 # cigar_int_to_len / _to_op, ssw.c:878-904
+        for val in self._cigar_string:
+            yield (val >> 4, "MIDNSHP=X"[val & 15] if val & 15 < 9 else "M")
+
+    @property
+    def cigar_string(self):                                               # ssw_wrap.py:320-345
+        if len(self._cigar_string) == 0:
+            return ""
+        out = "{}S".format(self.query_begin) if self.query_begin > 0 else ""
+        out += "".join("{}{}".format(n, op) for n, op in self.iter_cigar)
+        end_len = len(self.query_seq) - self.query_end - 1
+        if end_len != 0:
+            out += "{}S".format(end_len)
+        return out
+    cigar = cigar_string
+
+    @property
+    def alignment(self):                                                  # ssw_wrap.py:348-383
+        r, q = self.ref_begin if self.ref_begin > 0 else 0, self.query_begin if self.query_begin > 0 else 0
+        r_line = m_line = q_line = ""
+        for n, op in self.iter_cigar:
+            if op == "M":
+                rs, qs = self.ref_seq[r:r + n], self.query_seq[q:q + n]
+                r_line += rs
+                q_line += qs
+                m_line += "".join("|" if a == b else "*" for a, b in zip(rs, qs))
+                r, q = r + n, q + n
+            elif op == "I":
+                r_line += " " * n
+                m_line += " " * n
+                q_line += self.query_seq[q:q + n]
+                q += n
+            elif op == "D":
+                r_line += self.ref_seq[r:r + n]
+                m_line += " " * n
+                q_line += " " * n
+                r += n
+        return (r_line, m_line, q_line)
 
 
 class Aligner(object):
@@ -32,6 +88,7 @@ class Aligner(object):
                  report_cigar=False, ctx=None):
         self.ref_seq = ref_seq
         self.match, self.mismatch, self.gap_open, self.gap_extend = match, mismatch, gap_open, gap_extend
+        self.report_cigar = bool(report_cigar)   # the reference computes the CIGAR on every call; here it is opt-in
         self._own = ctx            # a caller-supplied context is used as is (and its ladders replaced)
 
     def _ready(self):
@@ -56,11 +113,35 @@ class Aligner(object):
         p = _lib.SwParams(self.match, self.mismatch, self.gap_open, self.gap_extend, 9, 0, 0, 0)
         ctx.sw_classify(_lib.MEM_HOST, packed, woff, rlen, n, np.array([0, n], np.int32), np.zeros(1, np.int32), 1, p,
                         tag, h, sc, dump, 1)
-        out = []
-        for q, rec in zip(queries, dump[:, 0]):
-            keep = int(rec[0]) >= min_score and int(rec[4]) - int(rec[3]) + 1 >= min_len    # ssw_wrap.py:214-220
-            out.append(PyAlignRes(rec, q, self.ref_seq) if keep else None)
-        return out
+        recs = dump[:, 0]
+        keep = [int(rec[0]) >= min_score and int(rec[4]) - int(rec[3]) + 1 >= min_len for rec in recs]    # ssw_wrap.py:214-220
+        ops = [()] * n
+        if self.report_cigar and any(keep):
+            ops = self._cigars(ctx, queries, recs, [k for k in range(n) if keep[k]], p, ops)
+        return [PyAlignRes(rec, q, self.ref_seq, o) if k else None for q, rec, k, o in zip(queries, recs, keep, ops)]
+
+    def _cigars(self, ctx, queries, recs, kept, p, ops):
+        """ONE sw_cigar call for the queries that passed the filter; a CIGAR longer than the room gets a second call."""
+        sub = [queries[k] for k in kept]
+        m = len(sub)
+        packed, woff, rlen = _lib.pack_reads(sub)
+        fields = np.ascontiguousarray(recs[kept, :5], np.int16)
+        zero = np.zeros(m, np.int32)
+        cap = 32
+        while True:
+            out, n_ops, status = np.zeros((m, cap), np.uint32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+            ctx.sw_cigar(_lib.MEM_HOST, packed, woff, rlen, m, zero, zero, fields, p, cap, out, n_ops, status,
+                         ladders=[(self.ref_seq, "A", "", 0)])
+            if not (status == _lib.CIGAR_OVERFLOW).any():
+                break
+            cap = int(n_ops.max())
+        ops = list(ops)
+        for i, k in enumerate(kept):
+            if status[i] != _lib.CIGAR_OK:
+                raise _lib.TredGpuError("sw_cigar: status {} for query {} (the reference runs off its buffers there)".format(
+                    int(status[i]), k))
+            ops[k] = out[i, :n_ops[i]]
+        return ops
 
     def align(self, query_seq, min_score=0, min_len=0):
         return self.align_many([query_seq], min_score, min_len)[0]

@@ -84,6 +84,8 @@ def set_argparse():
     p.add_argument("--noalts", action="store_true", help="skip the alternative loci where repeat reads get mismapped")
     p.add_argument("--norepeatpairs", action="store_true", help="discard pairs whose reads are both repeat-only")
     p.add_argument("--log", choices=("INFO", "DEBUG"), default="INFO", help="log level")
+    p.add_argument("--alignments", action="store_true",
+                   help="also write <samplekey>.alignments.txt: how every read of `details` was laid on the allele it was counted for")
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     p.add_argument("--toy", action="store_true", help=argparse.SUPPRESS)
     g = p.add_argument_group("Performance options")
@@ -245,6 +247,8 @@ def _genotype(engine, picks, o):
             return
         br = engine.genotype_packed(batch, dense=True) if o["log"] == "DEBUG" else engine.genotype_packed(batch)
         br.repeatpairs = kw["repeatpairs"]
+        if o["alignments"]:
+            br.alignments = engine.alignments(_alignment_units(sub, o["clip"]))
         i = 0
         for si, _, ks in sub:
             if ks:
@@ -267,6 +271,36 @@ def _genotype(engine, picks, o):
     return out
 
 
+def _alignment_units(sub, clip):
+    """The units of _genotype's picks, in the batch's order, as Engine.alignments takes them: their reads as text."""
+    from .engine import Unit
+    units = []
+    for _, s, ks in sub:
+        for k in ks:
+            a, b = s.reads_of(k)
+            units.append(Unit(s.loci[k], s.readlen, [s.sequence(i) for i in range(a, b)], s.depth[k], s.ploidy[k], (), (), clip=clip))
+    return units
+
+
+def alignments_text(scan, calls, res, repeatpairs):
+    """--alignments: for every `details` entry of every called locus, in `details` order, a header line
+    `>{locus} {tag} h={h} {+|-} {read id}` (- : the template's reverse complement), the reference's verbose block for the
+    pair (bam_parser.py:145-147) and a blank line.  res: {locus index: UnitResult with .alignments}."""
+    from ._lib import TAG_NAMES
+    out = []
+    for k, name in enumerate(scan.names):
+        r = res.get(k)
+        if r is None or name + ".details" not in calls:
+            continue
+        _, details, _ = tally(scan, k, r.tags, r.hs, repeatpairs=repeatpairs, lazy=True)
+        a, _ = scan.reads_of(k)
+        for i, t, h in zip(details.reads.tolist(), details.tags.tolist(), details.hs.tolist()):
+            x = r.alignments[i - a]
+            assert (x.tag, x.h) == (t, h)
+            out.append(">{} {} h={} {} {}\n{}\n".format(name, TAG_NAMES[t], h, "-" if x.strand else "+", scan.name(i), x.verbose()))
+    return "".join(out)
+
+
 def genotype_scans(engine, task_args, scans):
     """GPU half of a batch: the kernels' results for every unit of the scans, (picks, parts) with parts as _genotype
     returns them (unit_results turns them into per-unit views).
@@ -284,7 +318,7 @@ def genotype_scans(engine, task_args, scans):
         o = _options(arg)
         # (a scan whose reads the device selected and still holds -- feeder._device_scan -- goes to the call that packs them there)
         on_device = getattr(pick[1], "device", None) is not None
-        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", on_device)
+        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", o["alignments"], on_device)
         groups.setdefault(key, (o, []))[1].append(pick)
     parts = {}
 
@@ -842,7 +876,8 @@ def main(args, quiet=False):
         if args.checkexists and not spawned:
             samples = [s for s in samples if not os.path.exists(s[0] + ".json")]
         tasks = [(key, bam, repo, [only] if only else loci, args.maxinsert, args.fullsearch, args.useclippedreads,
-                  not args.noalts, not args.norepeatpairs, args.log) for key, bam, only in samples]
+                  not args.noalts, not args.norepeatpairs, args.log) + ((True,) if args.alignments else ())
+                 for key, bam, only in samples]
         if not tasks:
             return
         drivers = 1
