@@ -39,8 +39,9 @@ def _set_x(w, i, j):
     return j - (x if x > 0 else 0)
 
 
-def banded_cigar(ref, read, score, match=1, mismatch=5, gap_open=7, gap_extend=2):
-    """ref, read: code lists of the sub-rectangle.  Returns (status, [ops])."""
+def banded_cigar(ref, read, score, match=1, mismatch=5, gap_open=7, gap_extend=2, passes=None):
+    """ref, read: code lists of the sub-rectangle.  Returns (status, [ops]).  passes: a list that receives (band, banded
+    maximum so far) of every pass the model ran, in order."""
     ref_len, read_len = len(ref), len(read)
     cover = max(ref_len, read_len) - 1
     bw = abs(ref_len - read_len) + 1
@@ -75,6 +76,8 @@ def banded_cigar(ref, read, score, match=1, mismatch=5, gap_open=7, gap_extend=2
                 dirs[width_d * i + _set_x(bw, i, j)] = (de, df, dh)
             for j in range(1, u + 1):
                 h_b[j] = h_c[j]
+        if passes is not None:
+            passes.append((bw, best))
         if best >= score:
             break
         if bw >= cover:
@@ -117,6 +120,43 @@ def cigar_of(ref_seq, query_seq, fields, match=1, mismatch=5, gap_open=7, gap_ex
     score, rb, re_, qb, qe = (int(v) for v in fields[:5])
     return banded_cigar(encode(ref_seq)[rb:re_ + 1], encode(query_seq)[qb:qe + 1], score, match, mismatch, gap_open,
                         gap_extend)
+
+
+def passes_of(ref_seq, query_seq, fields, match=1, mismatch=5, gap_open=7, gap_extend=2):
+    """(status, [ops], [(band, banded maximum so far)] of every pass the model ran for the item)."""
+    score, rb, re_, qb, qe = (int(v) for v in fields[:5])
+    passes = []
+    st, ops = banded_cigar(encode(ref_seq)[rb:re_ + 1], encode(query_seq)[qb:qe + 1], score, match, mismatch, gap_open,
+                           gap_extend, passes)
+    return st, ops, passes
+
+
+def bands_of(ref_seq, query_seq, fields, match=1, mismatch=5, gap_open=7, gap_extend=2):
+    """The sequence of bands the model ran for the item (band 1, 2, 4 ... while the banded maximum is below the score)."""
+    return [b for b, _ in passes_of(ref_seq, query_seq, fields, match, mismatch, gap_open, gap_extend)[2]]
+
+
+_limits = {}
+
+
+def narrow_limits():
+    """(NARROW_ROW, NARROW_PLANE) as tredparse_amd/csrc/sw_cigar.hip declares them."""
+    if not _limits:
+        import os
+        import re
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        src = open(os.path.join(root, "tredparse_amd", "csrc", "sw_cigar.hip")).read()
+        for name in ("NARROW_ROW", "NARROW_PLANE"):
+            _limits[name] = int(re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, src).group(1))
+    return _limits["NARROW_ROW"], _limits["NARROW_PLANE"]
+
+
+def is_wide(bands, read_len):
+    """The tier the kernel finishes an item in, predicted from the bands the model ran over its read_len rows: the narrow
+    kernel hands the item on at the first pass whose row (2 * band + 3 entries) or plane ((2 * band + 1) * read_len
+    cells) does not fit its storage."""
+    row, plane = narrow_limits()
+    return any(2 * b + 3 > row - 1 or (2 * b + 1) * read_len > plane for b in bands)
 
 
 def consumed(ops):
@@ -179,3 +219,27 @@ def golden():
                        ops=[[int(v) for v in g["ops"][off[k]:off[k + 1]]] for k in range(len(off) - 1)])
         _golden["refs"] = [template(ladders[l], int(t)) for l, t in zip(_golden["ladder"], _golden["template"])]
     return _golden
+
+
+_golden_scorings = {}
+
+
+def golden_scorings():
+    """tests/golden/sw_cigar_scorings.npz (tools/gen_golden_cigar.py --scoring), loaded once: as golden(), with scoring
+    ((match, mismatch, gap_open, gap_extend) per item) and cigar_string (the reference's text per item)."""
+    if not _golden_scorings:
+        import json
+        import os
+        import numpy as np
+        g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sw_cigar_scorings.npz"))
+        meta = json.loads(str(g["meta"]))
+        ladders = [(l[0], l[1], l[2], int(l[3])) for l in meta["ladders"]]
+        off = g["ops_off"]
+        _golden_scorings.update(
+            ladders=ladders, cls=[str(c) for c in g["cls"]], ladder=g["ladder"].astype(np.int32),
+            template=g["template"].astype(np.int32), reads=[str(r) for r in g["reads"]], fields=g["fields"].astype(np.int16),
+            scoring=[tuple(int(v) for v in row) for row in g["scoring"]], cigar_string=meta["cigar_string"], meta=meta,
+            ops=[[int(v) for v in g["ops"][off[k]:off[k + 1]]] for k in range(len(off) - 1)])
+        _golden_scorings["refs"] = [template(ladders[l], int(t)) for l, t in
+                                    zip(_golden_scorings["ladder"], _golden_scorings["template"])]
+    return _golden_scorings

@@ -35,6 +35,55 @@ def test_golden_operations_consume_the_rectangle_and_rescore():
         assert cm.rescore(ref, read, f, ops) == f[0], k
 
 
+SCORINGS = ((2, 2, 3, 1), (1, 1, 2, 1), (1, 4, 6, 1), (3, 5, 7, 2), (4, 9, 10, 10), (8, 16, 16, 16), (1, 0, 1, 1), (1, 5, 7, 7))
+
+
+def test_scoring_goldens_are_what_the_generator_promises():
+    g = cm.golden_scorings()
+    meta = g["meta"]
+    assert set(g["scoring"]) == set(SCORINGS) and meta["scorings"] == ["/".join(map(str, s)) for s in SCORINGS]
+    for s in SCORINGS:
+        text = "/".join(map(str, s))
+        ks = [k for k, v in enumerate(g["scoring"]) if v == s]
+        assert len(ks) == meta["kept"][text] >= 55
+        assert meta["excluded"][text] <= 0.02 * (meta["kept"][text] + meta["excluded"][text])
+        assert {g["cls"][k] for k in ks} == set("bcde")
+        lens = [len(g["reads"][k]) for k in ks]
+        assert min(lens) <= 36 and max(lens) == 250
+        assert sum(1 for k in ks if any(v & 15 for v in g["ops"][k])) >= 10, text             # items with a gap
+        assert sum(1 for k in ks if len(g["ops"][k]) > 3) >= 10, text
+    assert len(g["cigar_string"]) == len(g["reads"])
+
+
+def test_model_reproduces_every_golden_cigar_at_its_scoring():
+    g = cm.golden_scorings()
+    for k, (ref, read, f, want, s) in enumerate(zip(g["refs"], g["reads"], g["fields"], g["ops"], g["scoring"])):
+        status, ops = cm.cigar_of(ref, read, f, *s)
+        assert status == cm.OK and ops == want, (k, s, g["cls"][k], status, ops, want)
+        assert cm.consumed(ops) == (f[4] - f[3] + 1, f[2] - f[1] + 1), (k, s)
+        assert cm.rescore(ref, read, f, ops, *s) == f[0], (k, s)
+        al = PyAlignRes(f, read, ref, ops)
+        assert al.cigar_string == g["cigar_string"][k], (k, s)
+
+
+def test_bands_helper_and_predicted_tier():
+    """bands_of / is_wide: the band starts at |refLen - readLen| + 1 and doubles up to the rectangle's cover; the limits are
+    the kernel's own constants."""
+    row, plane = cm.narrow_limits()
+    assert row >= 8 and plane >= 1024
+    ref = "ACGTTGCAAGCTTAGGCTAACGTAGCTAGGATCCGATTACA" * 3
+    read = ref[5:65]
+    assert cm.bands_of(ref, read, (30, 5, 64, 0, 59)) == [1]
+    assert cm.bands_of(ref, read, (30, 5, 74, 0, 59)) == [11]
+    assert cm.bands_of(ref, read, (999, 5, 64, 0, 59)) == [1, 2, 4, 8, 16, 32, 59]             # NO_PATH at full cover
+    st, ops, passes = cm.passes_of(ref, read, (999, 5, 64, 0, 59))
+    assert (st, ops) == (cm.NO_PATH, []) and [b for _, b in passes] == [60] * 7
+    top = (row - 4) // 2                                    # the widest band whose 2 * band + 3 entries fit a row of row - 1
+    fit = plane // (2 * top + 1)
+    assert not cm.is_wide([1, 2, top], fit) and cm.is_wide([top], fit + 1) and cm.is_wide([1, 2, top + 1], 10)
+    assert not cm.is_wide([1], plane // 3) and cm.is_wide([1], plane // 3 + 1)
+
+
 def test_band_doubles_for_compensating_indels():
     """Class d: refLen == readLen, so the band starts at 1; a 3-base deletion and a 3-base insertion need it at 4."""
     g = cm.golden()

@@ -7,6 +7,8 @@ re-draws them: the long campaigns logged under profiles/ are the same code with 
   fuzz_selfcheck  production launch vs arg-max over the unpruned per-template dump (GPU only, many reads)
   fuzz_hist       adversarial grid inputs vs the numpy oracle: status, enumeration, four terms per pair, CI, PP
   fuzz_grid       SW -> histograms -> grid on random synthetic batches vs the numpy oracle
+  fuzz_cigar      the CIGAR kernel vs the reference's own compiled banded_sw (oracle/_ref; without it tests/cigar_model.py,
+                  which tests/test_cigar_model.py pins to the reference) pair by pair at six scorings: every operation
 """
 import os
 import sys
@@ -51,3 +53,13 @@ def test_fuzz_inflate_slice():
     res = fuzz_inflate.campaign(rounds=6, seed=20270305)
     assert res["streams"] == 1800 and res["intact"] == 1440 and res["damaged_refused"] > 100
     assert res["mismatches"] == 0, res
+
+
+def test_fuzz_cigar_slice():
+    import fuzz_cigar
+    scorings = ((1, 5, 7, 2), (2, 2, 3, 1), (1, 1, 2, 1), (1, 4, 6, 1), (3, 5, 7, 2), (1, 0, 1, 1))
+    res = fuzz_cigar.campaign(n=1500, seed=20270306, scorings=scorings)
+    assert res["mismatches"] == 0, res
+    assert res["compared"] >= 0.9 * res["pairs"] == 1350, res
+    assert 2 * res["with_gap"] > res["compared"], res
+    assert res["wide_tier"] >= 1, res

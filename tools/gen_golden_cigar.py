@@ -8,7 +8,11 @@ driven through the reference's ssw_wrap.Aligner / PyAlignRes (tools/refshim.py),
 reference's CIGAR pass (oracle/ref_driver.c:15-23) ends one child, loses that one item, and a fresh child goes on
 with the rest.  Nothing of the reference is stored, only these inputs and outputs.
 
-Scoring is 1/5/7/2 throughout (bam_parser.py:95-98).  Items:
+    python tools/gen_golden_cigar.py                        tests/golden/sw_cigar.npz at 1/5/7/2 (and the report)
+    python tools/gen_golden_cigar.py --scoring 2/2/3/1 ...   tests/golden/sw_cigar_scorings.npz: a draw of its own of the
+                                                            classes b-e (reads of 36-250 bp) per scoring given
+
+Scoring is 1/5/7/2 (bam_parser.py:95-98) unless --scoring says otherwise.  Items:
   a  the winning (read, template) pair of every `details` read of t001/HD and t002/DM1 (run_t001_t002.json)
   b  synthetic reads of 36/100/150/250/480 bp on ladders of period 3/4/5/6/12, both strands, 1 % substitutions and N
   c  the same reads against a template one or two units off: a single I or D of 3-24 bases, band > 1 from the start
@@ -33,6 +37,13 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SCORING = dict(match=1, mismatch=5, gap_open=7, gap_extend=2)
+SCORINGS_FILE = os.path.join(ROOT, "tests", "golden", "sw_cigar_scorings.npz")
+
+
+def parse_scoring(text):
+    """'m/x/o/e' -> the Aligner's keyword arguments."""
+    m, x, o, e = (int(v) for v in text.split("/"))
+    return dict(match=m, mismatch=x, gap_open=o, gap_extend=e)
 COMP = {"A": "T", "C": "G", "G": "C", "T": "A", "N": "N"}
 
 
@@ -50,7 +61,7 @@ def template(ladder, t):
 
 
 # ---- the child: the reference, item by item -----------------------------------------------------------------------
-def worker():
+def worker(scoring=SCORING):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import refshim
     ref = refshim.load_reference()
@@ -59,7 +70,7 @@ def worker():
     res_cls.cigar_int_to_op = staticmethod(lambda v: raw_op(v).decode())     # c_char is bytes under Python 3
     for line in sys.stdin:
         ref_seq, read = json.loads(line)
-        al = ref.ssw.Aligner(ref_seq=ref_seq, report_secondary=False, **SCORING).align(read)
+        al = ref.ssw.Aligner(ref_seq=ref_seq, report_secondary=False, **scoring).align(read)
         out = {"fields": [al.score, al.ref_begin, al.ref_end, al.query_begin, al.query_end],
                "ops": [int(v) & 0xFFFFFFFF for v in al._cigar_string], "cigar_string": al.cigar_string,
                "alignment": list(al.alignment), "str": str(al)}
@@ -67,13 +78,14 @@ def worker():
         sys.stdout.flush()
 
 
-def run_reference(pairs, chunk=200):
+def run_reference(pairs, chunk=200, scoring=SCORING):
     """[result dict or None (the reference faulted)] for every (ref_seq, read)."""
     out = [None] * len(pairs)
     k = 0
+    tag = "{match}/{mismatch}/{gap_open}/{gap_extend}".format(**scoring)
     while k < len(pairs):
         part = pairs[k:k + chunk]
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"], input="".join(json.dumps(x) + "\n" for x in part),
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", tag], input="".join(json.dumps(x) + "\n" for x in part),
                            stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, universal_newlines=True)
         lines = [l for l in p.stdout.split("\n") if l.endswith("}")]
         for i, l in enumerate(lines):
@@ -263,5 +275,105 @@ def main():
         ops=np.array([v for k in kept for v in k[4]["ops"]], np.uint32), meta=np.array(json.dumps(meta)))
 
 
+def build_small(rng):
+    """About 60 items of the classes b-e with reads of 36-250 bp: (ladders, items) as build() gives them."""
+    ladders, items = [], []
+
+    def ladder_id(l):
+        ladders.append(tuple(l))
+        return len(ladders) - 1
+
+    motifs = {3: "CAG", 4: "CCTG", 5: "ATTCT", 6: "GGCCTG", 12: "CCCCGCCCCGCG"}
+    for readlen in (36, 100, 150, 250):                               # b: periodic ladders, both strands
+        for period in rng.sample(sorted(motifs), 2):
+            mu = -(-readlen // period)
+            lad = ladder_id((randseq(rng, 30), motifs[period], randseq(rng, 30), mu))
+            for strand in (0, 1):
+                u = mu if strand == 0 else rng.randint(max(1, mu // 4), mu)
+                src = template(ladders[lad], 2 * (u - 1) + strand)
+                L = min(readlen, len(src))
+                at = rng.choice([0, len(src) - L, rng.randint(0, len(src) - L)])
+                items.append(("b", lad, 2 * (u - 1) + strand, mutate(rng, src[at:at + L])))
+    for period, motif in sorted(motifs.items()):                      # c: a unit or two off, read end to end
+        for k in range(2):
+            mu = -(-150 // period)
+            lad = ladder_id((randseq(rng, 20), motif, randseq(rng, 20), mu))
+            u = rng.randint(3, min(mu - 2, 100 // period))
+            strand = k % 2
+            read = mutate(rng, template(ladders[lad], 2 * (u - 1) + strand), n=0.0)
+            for off in rng.sample([-2, -1, 1, 2], 2):
+                if 1 <= u + off <= mu and abs(off) * period <= 24:
+                    items.append(("c", lad, 2 * (u + off - 1) + strand, read))
+    for k in range(14):                                               # d: compensating indels on plain references
+        g = rng.choice([1, 3, 3, 6])
+        n = rng.choice([100, 150, 200, 250])
+        ref = randseq(rng, n + 20)
+        p1 = rng.randint(25, n // 2 - 10)
+        p2 = p1 + rng.randint(30, n - 25 - p1)
+        body = ref[10:10 + n]
+        if k % 2:
+            read = body[:p1] + body[p1 + g:p2] + randseq(rng, g) + body[p2:]
+        else:
+            read = body[:p1] + randseq(rng, g) + body[p1:p2] + body[p2 + g:]
+        items.append(("d", ladder_id((ref, "A", "", 0)), 0, mutate(rng, read)))
+    for k in range(14):                                               # e: an indel close to an end, or a long one
+        n = rng.choice([36, 60, 100, 150])
+        ref = randseq(rng, n + 30)
+        body = ref[15:15 + n]
+        g, d = (rng.randint(1, 3), rng.randint(8, 16)) if k < 8 else (rng.choice([12, 24]), n // 2 - 12)
+        p = d if k % 2 else n - d - g
+        read = body[:p] + body[p + g:] if k % 4 < 2 else body[:p] + randseq(rng, g) + body[p:]
+        items.append(("e", ladder_id((ref, "A", "", 0)), 0, read))
+    return ladders, items
+
+
+def main_scorings(texts):
+    """tests/golden/sw_cigar_scorings.npz: per scoring a draw of build_small, the reference's fields and operations."""
+    ladders, rows, kept_n, excl_n, cigars = [], [], {}, {}, []
+    for text in texts:
+        scoring = parse_scoring(text)
+        rng = random.Random("20261018 " + text)
+        lads, items = build_small(rng)
+        res = run_reference([(template(lads[lad], t), read) for _, lad, t, read in items], scoring=scoring)
+        kept = 0
+        for (c, lad, t, read), r in zip(items, res):
+            ok = r is not None and len(r["ops"]) > 0
+            if ok:
+                q = sum(v >> 4 for v in r["ops"] if v & 15 in (0, 1))
+                rr = sum(v >> 4 for v in r["ops"] if v & 15 in (0, 2))
+                f = r["fields"]
+                ok = q == f[4] - f[3] + 1 and rr == f[2] - f[1] + 1
+            if not ok:
+                continue
+            kept += 1
+            rows.append((c, len(ladders) + lad, t, read, r, [scoring[k] for k in ("match", "mismatch", "gap_open", "gap_extend")]))
+            cigars.append(r["cigar_string"])
+        ladders += lads
+        kept_n[text], excl_n[text] = kept, len(items) - kept
+        assert excl_n[text] <= 0.02 * len(items), (text, kept_n, excl_n)
+    used = sorted({r[1] for r in rows})                               # ladders no kept item refers to are dropped
+    renum = {l: i for i, l in enumerate(used)}
+    meta = {"generator": "tools/gen_golden_cigar.py --scoring: the reference's ssw_wrap.Aligner (src/ssw.c compiled, via "
+                         "tools/refshim.py), classes b-e, one draw per scoring", "scorings": list(texts),
+            "ladders": [list(ladders[l]) for l in used], "kept": kept_n, "excluded": excl_n,
+            "with_gap": {t: sum(1 for r in rows if "/".join(map(str, r[5])) == t and any(v & 15 for v in r[4]["ops"])) for t in texts},
+            "more_than_3_ops": {t: sum(1 for r in rows if "/".join(map(str, r[5])) == t and len(r[4]["ops"]) > 3) for t in texts},
+            "cigar_string": cigars}
+    print(json.dumps({k: v for k, v in meta.items() if k not in ("ladders", "cigar_string")}, indent=1))
+    ops_off = np.zeros(len(rows) + 1, np.int64)
+    ops_off[1:] = np.cumsum([len(r[4]["ops"]) for r in rows])
+    np.savez_compressed(
+        SCORINGS_FILE, cls=np.array([r[0] for r in rows]), ladder=np.array([renum[r[1]] for r in rows], np.int32),
+        template=np.array([r[2] for r in rows], np.int32), reads=np.array([r[3] for r in rows]),
+        fields=np.array([r[4]["fields"] for r in rows], np.int16), scoring=np.array([r[5] for r in rows], np.int32),
+        ops_off=ops_off, ops=np.array([v for r in rows for v in r[4]["ops"]], np.uint32), meta=np.array(json.dumps(meta)))
+
+
 if __name__ == "__main__":
-    worker() if "--worker" in sys.argv else main()
+    if "--worker" in sys.argv:
+        rest = sys.argv[sys.argv.index("--worker") + 1:]
+        worker(parse_scoring(rest[0]) if rest else SCORING)
+    elif "--scoring" in sys.argv:
+        main_scorings(sys.argv[sys.argv.index("--scoring") + 1:])
+    else:
+        main()
