@@ -168,6 +168,16 @@ def _ptr(a):
     raise TypeError("unsupported buffer type {}".format(type(a)))
 
 
+def _ladder_args(ladders):
+    """A list of (prefix, repeat, suffix, max_units) as the (n_ladders, prefix, repeat, suffix, max_units) arguments of
+    tredgpu_set_ladders, tredlong_sw_classify and tredcigar_sw_cigar.  The ctypes arrays own what they point to: the
+    caller holds the tuple until the call has returned."""
+    n = len(ladders)
+    arr = lambda k: (C.c_char_p * max(n, 1))(*[l[k].encode() for l in ladders])
+    mu = np.ctypeslib.as_ctypes(np.asarray([l[3] for l in ladders] or [0], np.int32))
+    return n, arr(0), arr(1), arr(2), mu
+
+
 def pack_reads(seqs):
     """2-bit + N-mask packing (tredgpu_pack_reads).  seqs: list of str/bytes.
     Returns (packed uint32[], word_off int64[n+1], read_len int32[n])."""
@@ -269,12 +279,9 @@ class Context:
             is_long = np.array([self._template_len(l) > MAX_TEMPLATE_LEN for l in ladders], bool)
             # the library's table: a plain one-letter reference stands in for a long ladder (none of its reads reaches it)
             native = [("N", "A", "", 0) if lg else l for l, lg in zip(ladders, is_long)]
-        n = len(native)
-        arr = lambda k: (C.c_char_p * max(n, 1))(*[l[k].encode() for l in native])
-        mu = np.asarray([l[3] for l in native] or [0], np.int32)
-        self._chk(self.lib.tredgpu_set_ladders(self.h, n, arr(0), arr(1), arr(2), mu.ctypes.data),
-                  "tredgpu_set_ladders")
-        self.n_ladders = n
+        table = _ladder_args(native)
+        self._chk(self.lib.tredgpu_set_ladders(self.h, *table), "tredgpu_set_ladders")
+        self.n_ladders = len(native)
         self.ladders, self._is_long = ladders, is_long
 
     # ---- the long-read path (include/tredlong.h) -------------------------------------------------------------
@@ -339,18 +346,13 @@ class Context:
         sub = np.ascontiguousarray(np.concatenate([pk[woff[r]:woff[r + 1]] for r in routed]), np.uint32)
         uro = np.asarray(unit_read_off)[:n_units + 1].astype(np.int64)
         lad = np.ascontiguousarray(np.repeat(np.asarray(unit_ladder)[:n_units], np.diff(uro))[routed], np.int32)
-        ladders = self.ladders
-        n_l = len(ladders)
-        arr = lambda k: (C.c_char_p * n_l)(*[l[k].encode() for l in ladders])
-        mu = np.asarray([l[3] for l in ladders], np.int32)
+        table = _ladder_args(self.ladders)
         m = len(routed)
         tag, h, sc = np.zeros(m, np.uint8), np.zeros(m, np.int16), np.zeros(m, np.int16)
         dump = np.zeros((m, dump_templates, 6), np.int16) if out_dump is not None else None
         sub_len = np.ascontiguousarray(rl[routed])      # (held here: _ptr keeps no reference)
-        prefixes, repeats, suffixes = arr(0), arr(1), arr(2)
-        rc = self.lib.tredlong_sw_classify(self.h, n_l, prefixes, repeats, suffixes, _ptr(mu), _ptr(sub), _ptr(sub_off),
-                                               _ptr(sub_len), m, _ptr(lad), C.byref(p),
-                                               _ptr(tag), _ptr(h), _ptr(sc), _ptr(dump), dump_templates if dump is not None else 0)
+        rc = self.lib.tredlong_sw_classify(self.h, *table, _ptr(sub), _ptr(sub_off), _ptr(sub_len), m, _ptr(lad), C.byref(p),
+                                           _ptr(tag), _ptr(h), _ptr(sc), _ptr(dump), dump_templates if dump is not None else 0)
         if rc != 0:
             raise TredGpuError("tredlong_sw_classify failed ({}): {}".format(rc, self.lib.tredlong_last_error().decode()))
         np.asarray(out_tag)[routed] = tag
@@ -490,12 +492,8 @@ class Context:
         item_ladder[k], placed by fields[k] = {score, ref_begin, ref_end, read_begin, read_end} (int16 [n][5]: a row of
         sw_classify's dump).  out_ops: uint32 [n][cap] (length << 4 | op, M=0 I=1 D=2), out_n_ops / out_status: int32 [n]
         (CIGAR_*).  ladders: the table the indices refer to (default: the one registered with set_ladders)."""
-        ladders = list(self.ladders if ladders is None else ladders)
-        n_l = len(ladders)
-        arr = lambda k: (C.c_char_p * max(n_l, 1))(*[l[k].encode() for l in ladders])
-        mu = np.asarray([l[3] for l in ladders] or [0], np.int32)
-        prefixes, repeats, suffixes = arr(0), arr(1), arr(2)
-        rc = self.lib.tredcigar_sw_cigar(self.h, mem, n_l, prefixes, repeats, suffixes, _ptr(mu), _ptr(packed), _ptr(read_off),
+        table = _ladder_args(list(self.ladders if ladders is None else ladders))
+        rc = self.lib.tredcigar_sw_cigar(self.h, mem, *table, _ptr(packed), _ptr(read_off),
                                          _ptr(read_len), n_items, _ptr(item_ladder), _ptr(item_template), _ptr(fields),
                                          C.byref(params), cap, _ptr(out_ops), _ptr(out_n_ops), _ptr(out_status))
         if rc != 0:

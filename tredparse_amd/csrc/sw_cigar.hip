@@ -19,18 +19,16 @@
 //     wavefront of 64 lanes with rows and plane in global memory: 1 026 entries per row array and 1 021 * 480 bytes of
 //     plane per lane (the band stops doubling once it covers the rectangle), 31 MB in all.
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <map>
 #include <mutex>
-#include <string>
-#include <vector>
 
 #include <hip/hip_runtime.h>
+#include "ladder_host.h"
 #include "../../include/tredcigar.h"
 
 namespace {
+using namespace ladder_host;
 
 struct CigarLadder {
     int32_t alen[2], blen[2];
@@ -224,20 +222,10 @@ __global__ __launch_bounds__(64) void cigar_wide_kernel(CigarArgs a) {
 // ---- host side ------------------------------------------------------------------------------------------------------
 thread_local std::string g_cigar_error;
 
-int cigar_fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_cigar_error = buf;
-    return code;
-}
-
-#define CIGCHK(expr)                                                                             \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return cigar_fail(-10, "%s: %s", #expr, hipGetErrorString(e_));    \
+#define CIGCHK(expr)                                                                                     \
+    do {                                                                                                 \
+        hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) return fail(g_cigar_error, -10, "%s: %s", #expr, hipGetErrorString(e_));   \
     } while (0)
 
 struct Dev {
@@ -280,74 +268,37 @@ int ensure(Dev& b, size_t bytes, hipStream_t st) {
     return 0;
 }
 
-int code_of(char ch) {
-    switch (ch) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': return 3;
-        default: return 4;
-    }
-}
-
-std::vector<uint8_t> codes_of(const char* s) {
-    std::vector<uint8_t> o;
-    for (; *s; ++s) o.push_back((uint8_t)code_of(*s));
-    return o;
-}
-
-std::vector<uint8_t> revcomp_of(const std::vector<uint8_t>& v) {
-    std::vector<uint8_t> o(v.size());
-    for (size_t i = 0; i < v.size(); ++i) {
-        const int c = v[v.size() - 1 - i];
-        o[i] = (uint8_t)(c == 4 ? 4 : 3 - c);
-    }
-    return o;
-}
-
 // the ladder table of the call (layout of tredgpu_set_ladders: trunk = prefix + repeat * max_units / rc(suffix) +
 // rc(repeat) * max_units, branch = suffix / rc(prefix)); uploaded only when it differs from the previous call's
 int set_ladders(State* s, hipStream_t st, int32_t n, const char* const* prefix, const char* const* repeat,
                 const char* const* suffix, const int32_t* max_units) {
     std::string key;
     for (int i = 0; i < n; ++i) {
-        if (!prefix[i] || !repeat[i] || !suffix[i]) return cigar_fail(-2, "ladder %d: NULL sequence", i);
+        if (!prefix[i] || !repeat[i] || !suffix[i]) return fail(g_cigar_error, -2, "ladder %d: NULL sequence", i);
         key += prefix[i]; key += '|'; key += repeat[i]; key += '|'; key += suffix[i]; key += '|';
         key += std::to_string(max_units[i]); key += ';';
     }
     if (s->n_ladders == n && key == s->ladder_key) return 0;
     std::vector<CigarLadder> lad((size_t)n);
     std::vector<uint8_t> pool;
-    auto append = [&pool](const std::vector<uint8_t>& v) {
+    auto append = [&pool](const Codes& v) {
         const int off = (int)pool.size();
         pool.insert(pool.end(), v.begin(), v.end());
         return off;
     };
+    Strands S;
     for (int i = 0; i < n; ++i) {
-        const std::vector<uint8_t> P = codes_of(prefix[i]), R = codes_of(repeat[i]), S = codes_of(suffix[i]);
-        const int mu = max_units[i];
         CigarLadder& d = lad[i];
         memset(&d, 0, sizeof d);
-        if (mu < 0) return cigar_fail(-2, "ladder %d: negative max_units", i);
-        d.period = (int)R.size();
-        d.max_units = mu;
-        if (mu == 0) {
-            d.alen[0] = (int)P.size();
-            d.trunk_off[0] = append(P);
-            continue;
-        }
-        if (R.empty()) return cigar_fail(-2, "ladder %d: empty repeat", i);
-        const std::vector<uint8_t> Pr = revcomp_of(P), Rr = revcomp_of(R), Sr = revcomp_of(S);
-        const std::vector<uint8_t>* A[2] = {&P, &Sr};
-        const std::vector<uint8_t>* Rep[2] = {&R, &Rr};
-        const std::vector<uint8_t>* B[2] = {&S, &Pr};
-        for (int k = 0; k < 2; ++k) {
-            std::vector<uint8_t> trunk(*A[k]);
-            for (int u = 0; u < mu; ++u) trunk.insert(trunk.end(), Rep[k]->begin(), Rep[k]->end());
-            d.alen[k] = (int)A[k]->size();
-            d.blen[k] = (int)B[k]->size();
-            d.trunk_off[k] = append(trunk);
-            d.branch_off[k] = append(*B[k]);
+        if (const char* why = build_strands(prefix[i], repeat[i], suffix[i], max_units[i], S))
+            return fail(g_cigar_error, -2, "ladder %d: %s", i, why);
+        d.period = S.period;
+        d.max_units = S.max_units;
+        for (int k = 0; k < S.n_strands; ++k) {
+            d.alen[k] = S.alen[k];
+            d.blen[k] = S.blen[k];
+            d.trunk_off[k] = append(S.trunk[k]);
+            d.branch_off[k] = append(S.branch[k]);
         }
     }
     pool.resize(pool.size() + 16, 4);
@@ -374,17 +325,15 @@ int tredcigar_sw_cigar(tredgpu_ctx* ctx, int mem, int32_t n_ladders, const char*
                        const int16_t* fields, const tredgpu_sw_params* p, int32_t cap, uint32_t* out_ops,
                        int32_t* out_n_ops, int32_t* out_status) {
     g_cigar_error.clear();
-    if (!ctx) return cigar_fail(-2, "ctx is NULL");
-    if (mem != TREDGPU_MEM_HOST && mem != TREDGPU_MEM_DEVICE) return cigar_fail(-2, "mem must be TREDGPU_MEM_HOST or TREDGPU_MEM_DEVICE");
-    if (n_items < 0 || n_items > 0x7fffffff || n_ladders <= 0 || cap <= 0) return cigar_fail(-2, "n_items, n_ladders and cap must be positive");
-    if (!prefix || !repeat || !suffix || !max_units) return cigar_fail(-2, "NULL ladder argument");
-    if (!p) return cigar_fail(-2, "params is NULL");
-    if (p->match < 1 || p->match > 8 || p->mismatch < 0 || p->mismatch > 16 || p->gap_open < 1 || p->gap_open > 16 ||
-        p->gap_extend < 1 || p->gap_extend > p->gap_open)
-        return cigar_fail(-2, "scoring out of the supported range (match 1..8, mismatch 0..16, 1 <= gap_extend <= gap_open <= 16)");
+    if (!ctx) return fail(g_cigar_error, -2, "ctx is NULL");
+    if (mem != TREDGPU_MEM_HOST && mem != TREDGPU_MEM_DEVICE) return fail(g_cigar_error, -2, "mem must be TREDGPU_MEM_HOST or TREDGPU_MEM_DEVICE");
+    if (n_items < 0 || n_items > 0x7fffffff || n_ladders <= 0 || cap <= 0) return fail(g_cigar_error, -2, "n_items, n_ladders and cap must be positive");
+    if (!prefix || !repeat || !suffix || !max_units) return fail(g_cigar_error, -2, "NULL ladder argument");
+    if (!p) return fail(g_cigar_error, -2, "params is NULL");
+    if (const char* why = scoring_refusal(*p, false)) return fail(g_cigar_error, -2, "%s", why);
     if (n_items == 0) return 0;
     if (!packed || !read_off || !read_len || !item_ladder || !item_template || !fields || !out_ops || !out_n_ops || !out_status)
-        return cigar_fail(-2, "NULL array argument");
+        return fail(g_cigar_error, -2, "NULL array argument");
     hipStream_t st = (hipStream_t)tredgpu_get_stream(ctx);
     int dev = 0;
     CIGCHK(hipStreamGetDevice(st, &dev));
@@ -397,7 +346,7 @@ int tredcigar_sw_cigar(tredgpu_ctx* ctx, int mem, int32_t n_ladders, const char*
     memset(&a, 0, sizeof a);
     const size_t n = (size_t)n_items;
     if (mem == TREDGPU_MEM_HOST) {
-        if (read_off[0] < 0 || read_off[n] < read_off[0]) return cigar_fail(-2, "read_off must be monotone");
+        if (read_off[0] < 0 || read_off[n] < read_off[0]) return fail(g_cigar_error, -2, "read_off must be monotone");
         const size_t sizes[9] = {(size_t)read_off[n] * 4, (n + 1) * 8, n * 4, n * 4, n * 4, n * 10,
                                  n * cap * sizeof(uint32_t), n * 4, n * 4};
         const void* src[6] = {packed, read_off, read_len, item_ladder, item_template, fields};
@@ -464,7 +413,7 @@ int tredcigar_sw_cigar(tredgpu_ctx* ctx, int mem, int32_t n_ladders, const char*
 }
 
 int tredcigar_get_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms) {
-    if (!ctx) return cigar_fail(-2, "ctx is NULL");
+    if (!ctx) return fail(g_cigar_error, -2, "ctx is NULL");
     State* s = state_of(ctx);
     CIGCHK(hipStreamSynchronize((hipStream_t)tredgpu_get_stream(ctx)));
     for (size_t i = 0; i < s->used; ++i) {

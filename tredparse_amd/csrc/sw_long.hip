@@ -20,12 +20,9 @@
 //    O(max_units^2) of separate alignments.
 // No pruning: every template of both strands is aligned (the path serves rare reads; the per-template dump needs all).
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
 
+#include "ladder_host.h"
 #include "tredgpu_internal.h"
 #include "../../include/tredlong.h"
 
@@ -259,46 +256,11 @@ __global__ __launch_bounds__(64) void sw_long_kernel(SwArgs a, const LongLadder*
 
 // ---- C entry points (include/tredlong.h) ----------------------------------------------------------------------
 using namespace tredgpu;
+using namespace ladder_host;
 
 namespace {
 
 thread_local std::string g_long_error;
-
-int long_fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_long_error = buf;
-    return code;
-}
-
-int long_code(char ch) {
-    switch (ch) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': return 3;
-        default: return 4;
-    }
-}
-
-std::vector<int8_t> long_encode(const char* s) {
-    std::vector<int8_t> o;
-    for (; *s; ++s) o.push_back((int8_t)long_code(*s));
-    return o;
-}
-
-// reverse complement on codes (N stays N): bam_parser.py:448-450
-std::vector<int8_t> long_revcomp(const std::vector<int8_t>& v) {
-    std::vector<int8_t> o(v.size());
-    for (size_t i = 0; i < v.size(); ++i) {
-        const int c = v[v.size() - 1 - i];
-        o[i] = (int8_t)(c == 4 ? 4 : 3 - c);
-    }
-    return o;
-}
 
 // device buffers of one call, released on every way out
 struct DevBufs {
@@ -313,10 +275,10 @@ struct DevBufs {
     }
 };
 
-#define LCHK(expr)                                                                                  \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return long_fail(-10, "%s: %s", #expr, hipGetErrorString(e_));        \
+#define LCHK(expr)                                                                                       \
+    do {                                                                                                 \
+        hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) return fail(g_long_error, -10, "%s: %s", #expr, hipGetErrorString(e_));    \
     } while (0)
 
 }  // namespace
@@ -331,19 +293,16 @@ int tredlong_sw_classify(tredgpu_ctx* ctx, int32_t n_ladders, const char* const*
                              const tredgpu_sw_params* p, uint8_t* out_tag, int16_t* out_h, int16_t* out_score,
                              int16_t* out_dump, int32_t dump_templates) {
     g_long_error.clear();
-    if (!ctx || !p) return long_fail(-2, "ctx or params is NULL");
-    if (n_ladders <= 0 || !prefix || !repeat || !suffix || !max_units) return long_fail(-2, "bad ladder arguments");
-    if (n_reads < 0) return long_fail(-2, "negative n_reads");
+    if (!ctx || !p) return fail(g_long_error, -2, "ctx or params is NULL");
+    if (n_ladders <= 0 || !prefix || !repeat || !suffix || !max_units) return fail(g_long_error, -2, "bad ladder arguments");
+    if (n_reads < 0) return fail(g_long_error, -2, "negative n_reads");
     if (n_reads > 0 && (!packed || !read_off || !read_len || !read_ladder || !out_tag || !out_h || !out_score))
-        return long_fail(-2, "NULL array argument");
-    if (out_dump && dump_templates <= 0) return long_fail(-2, "dump_templates must be > 0 with out_dump");
-    if (p->match < 1 || p->match > 8 || p->mismatch < 0 || p->mismatch > 16 || p->gap_open < 1 || p->gap_open > 16 ||
-        p->gap_extend < 1 || p->gap_extend > 16 || p->gap_extend > p->gap_open || p->flank < 0 || p->flank > 255)
-        return long_fail(-2, "scoring out of the supported range (match 1..8, mismatch 0..16, "
-                             "1 <= gap_extend <= gap_open <= 16, flank 0..255)");
+        return fail(g_long_error, -2, "NULL array argument");
+    if (out_dump && dump_templates <= 0) return fail(g_long_error, -2, "dump_templates must be > 0 with out_dump");
+    if (const char* why = scoring_refusal(*p, true)) return fail(g_long_error, -2, "%s", why);
     // ladders: the layout of tredgpu_set_ladders (letters 8 per word, every segment on a word boundary)
     std::vector<uint32_t> seq;
-    auto append = [&seq](const std::vector<int8_t>& v) {
+    auto append = [&seq](const Codes& v) {
         const int off = (int)seq.size();
         seq.resize(seq.size() + (v.size() + 7) / 8 + 1, 0x44444444u);
         for (size_t i = 0; i < v.size(); ++i) {
@@ -353,42 +312,27 @@ int tredlong_sw_classify(tredgpu_ctx* ctx, int32_t n_ladders, const char* const*
         return off;
     };
     std::vector<LongLadder> lad((size_t)n_ladders);
+    Strands S;
     for (int i = 0; i < n_ladders; ++i) {
-        const std::vector<int8_t> P = long_encode(prefix[i]), Rp = long_encode(repeat[i]), S = long_encode(suffix[i]);
-        const int mu = max_units[i];
         LadderDesc& d = lad[i].d;
         memset(&lad[i], 0, sizeof lad[i]);
-        if (mu < 0) return long_fail(-2, "ladder %d: negative max_units", i);
-        if (mu == 0) {
-            if (P.empty() || P.size() > TREDGPU_MAX_LONG_TEMPLATE_LEN)
-                return long_fail(-2, "ladder %d: reference length %zu not in [1,%d]", i, P.size(), TREDGPU_MAX_LONG_TEMPLATE_LEN);
-            d.alen[0] = (int)P.size();
-            d.trunk_off[0] = append(P);
-            d.branch_off[0] = append(std::vector<int8_t>());
-            d.period = 1;
-            d.n_strands = 1;
-            continue;
-        }
-        if (Rp.empty()) return long_fail(-2, "ladder %d: empty repeat", i);
-        const size_t T = P.size() + S.size() + Rp.size() * (size_t)mu;
+        if (const char* why = build_strands(prefix[i], repeat[i], suffix[i], max_units[i], S))
+            return fail(g_long_error, -2, "ladder %d: %s", i, why);
+        const size_t T = (size_t)S.alen[0] + S.blen[0] + (size_t)S.period * S.max_units;
+        if (S.max_units == 0 && (T < 1 || T > TREDGPU_MAX_LONG_TEMPLATE_LEN))
+            return fail(g_long_error, -2, "ladder %d: reference length %zu not in [1,%d]", i, T, TREDGPU_MAX_LONG_TEMPLATE_LEN);
         if (T > TREDGPU_MAX_LONG_TEMPLATE_LEN)
-            return long_fail(-2, "ladder %d: longest template %zu exceeds TREDGPU_MAX_LONG_TEMPLATE_LEN=%d", i, T,
-                             TREDGPU_MAX_LONG_TEMPLATE_LEN);
-        const std::vector<int8_t> Pr = long_revcomp(P), Rr = long_revcomp(Rp), Sr = long_revcomp(S);
-        const std::vector<int8_t>* A[2] = {&P, &Sr};
-        const std::vector<int8_t>* Rep[2] = {&Rp, &Rr};
-        const std::vector<int8_t>* B[2] = {&S, &Pr};
-        for (int s = 0; s < 2; ++s) {
-            d.alen[s] = (int)A[s]->size();
-            d.blen[s] = (int)B[s]->size();
-            std::vector<int8_t> trunk(*A[s]);
-            for (int k = 0; k < mu; ++k) trunk.insert(trunk.end(), Rep[s]->begin(), Rep[s]->end());
-            d.trunk_off[s] = append(trunk);
-            d.branch_off[s] = append(*B[s]);
+            return fail(g_long_error, -2, "ladder %d: longest template %zu exceeds TREDGPU_MAX_LONG_TEMPLATE_LEN=%d", i, T,
+                        TREDGPU_MAX_LONG_TEMPLATE_LEN);
+        for (int s = 0; s < S.n_strands; ++s) {
+            d.alen[s] = S.alen[s];
+            d.blen[s] = S.blen[s];
+            d.trunk_off[s] = append(S.trunk[s]);
+            d.branch_off[s] = append(S.branch[s]);
         }
-        d.period = (int)Rp.size();
-        d.max_units = mu;
-        d.n_strands = 2;
+        d.period = S.max_units > 0 ? S.period : 1;     // a plain reference: one template, one unit column wide
+        d.max_units = S.max_units;
+        d.n_strands = S.n_strands;
     }
     seq.resize(seq.size() + 4, 0x44444444u);
     if (n_reads == 0) return 0;
@@ -397,10 +341,10 @@ int tredlong_sw_classify(tredgpu_ctx* ctx, int32_t n_ladders, const char* const*
     for (int64_t r = 0; r < n_reads; ++r) {
         const int L = read_len[r];
         if (L < 0 || L > TREDGPU_MAX_LONG_READ_LEN)
-            return long_fail(-5, "read of %d bp exceeds TREDGPU_MAX_LONG_READ_LEN=%d", L, TREDGPU_MAX_LONG_READ_LEN);
-        if (read_ladder[r] < 0 || read_ladder[r] >= n_ladders) return long_fail(-2, "read %lld: ladder %d not given", (long long)r, read_ladder[r]);
+            return fail(g_long_error, -5, "read of %d bp exceeds TREDGPU_MAX_LONG_READ_LEN=%d", L, TREDGPU_MAX_LONG_READ_LEN);
+        if (read_ladder[r] < 0 || read_ladder[r] >= n_ladders) return fail(g_long_error, -2, "read %lld: ladder %d not given", (long long)r, read_ladder[r]);
         if (read_off[r + 1] - read_off[r] != ((L + 15) >> 4) + ((L + 31) >> 5))
-            return long_fail(-2, "read %lld: read_off does not match read_len (tredgpu_pack_reads layout)", (long long)r);
+            return fail(g_long_error, -2, "read %lld: read_off does not match read_len (tredgpu_pack_reads layout)", (long long)r);
         lists[L <= 512 ? 0 : (L <= 1024 ? 1 : 2)].push_back(make_int2((int)r, read_ladder[r]));
     }
     hipStream_t st = (hipStream_t)tredgpu_get_stream(ctx);
