@@ -54,7 +54,9 @@ assert UNIT_DTYPE.itemsize == C.sizeof(UnitParams) == 64
 assert CALL_DTYPE.itemsize == C.sizeof(Call) == 56
 
 # the long-read path's symbols (include/tredlong.h)
-LONG_EXPORTS = ("tredlong_sw_classify", "tredlong_last_error")
+LONG_EXPORTS = ("tredlong_sw_classify", "tredlong_last_error", "tredlong_sw_cigar", "tredlong_cigar_timing",
+                "tredlong_cigar_reset_timing", "tredlong_release")
+LONG_CIGAR_SLOTS = 256          # wavefronts of a tredlong_sw_cigar launch at the most (csrc/cigar_long_plan.h)
 
 # the CIGAR kernel's symbols (include/tredcigar.h)
 CIGAR_EXPORTS = ("tredcigar_sw_cigar", "tredcigar_get_timing", "tredcigar_reset_timing", "tredcigar_release",
@@ -95,6 +97,12 @@ def load():
                                              C.POINTER(C.c_char_p), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, C.c_int32]
     lib.tredlong_last_error.argtypes = []
     lib.tredlong_last_error.restype = C.c_char_p
+    lib.tredlong_sw_cigar.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                      vp, vp, vp, vp, i64, vp, vp, vp, C.POINTER(SwParams), i32, vp, vp, vp]
+    lib.tredlong_cigar_timing.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
+    lib.tredlong_cigar_reset_timing.argtypes = [vp]
+    lib.tredlong_release.argtypes = [vp]
+    lib.tredlong_release.restype = None
     lib.tredcigar_sw_cigar.argtypes = [vp, C.c_int, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                        vp, vp, vp, vp, i64, vp, vp, vp, C.POINTER(SwParams), i32, vp, vp, vp]
     lib.tredcigar_get_timing.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
@@ -244,6 +252,7 @@ class Context:
     def close(self):
         if getattr(self, "h", None):
             self.lib.tredcigar_release(self.h)
+            self.lib.tredlong_release(self.h)
             self.lib.tredgpu_destroy(self.h)
             self.h = None
 
@@ -289,7 +298,8 @@ class Context:
         """Switch the long-read path on or off (off by default).  On: set_ladders accepts ladders up to
         MAX_LONG_TEMPLATE_LEN columns, and sw_classify, genotype_batch and genotype_batch_joint (host memory) accept reads
         up to MAX_LONG_READ_LEN bp.  A read longer than MAX_READ_LEN or on a ladder longer than MAX_TEMPLATE_LEN goes to
-        tredlong_sw_classify; every other read goes to the library's calls exactly as with the path off.  Refused
+        tredlong_sw_classify; every other read goes to the library's calls exactly as with the path off.  sw_cigar routes
+        its items the same way, to tredlong_sw_cigar.  Refused
         while a registered ladder is longer than MAX_TEMPLATE_LEN and the path is switched off."""
         enabled = bool(enabled)
         if not enabled and self._is_long is not None and self._is_long.any():
@@ -491,16 +501,85 @@ class Context:
         (packed / read_off / read_len as pack_reads writes them) against template item_template[k] (db order) of ladder
         item_ladder[k], placed by fields[k] = {score, ref_begin, ref_end, read_begin, read_end} (int16 [n][5]: a row of
         sw_classify's dump).  out_ops: uint32 [n][cap] (length << 4 | op, M=0 I=1 D=2), out_n_ops / out_status: int32 [n]
-        (CIGAR_*).  ladders: the table the indices refer to (default: the one registered with set_ladders)."""
-        table = _ladder_args(list(self.ladders if ladders is None else ladders))
+        (CIGAR_*).  ladders: the table the indices refer to (default: the one registered with set_ladders).
+        With the long-read path on (set_long_reads), an item whose read is longer than MAX_READ_LEN or whose ladder's
+        longest template is beyond MAX_TEMPLATE_LEN goes to tredlong_sw_cigar (include/tredlong.h; host memory only), all
+        of them in one call, and the rest to tredcigar_sw_cigar in one call, exactly as with the path off."""
+        ladders = list(self.ladders if ladders is None else ladders)
+        if self.long_reads and n_items > 0:
+            long_lad = np.array([self._template_len(l) > MAX_TEMPLATE_LEN for l in ladders], bool)
+            if mem != MEM_HOST:
+                if long_lad.any():
+                    raise TredGpuError("the long-read path takes host-memory calls (MEM_HOST) only")
+                if int(self._device_max(read_len, n_items)) > MAX_READ_LEN:
+                    raise TredGpuError("the long-read path takes host-memory calls (MEM_HOST) only: a read of the call is "
+                                       "longer than {} bp".format(MAX_READ_LEN))
+            else:
+                rl = np.asarray(read_len)[:n_items]
+                lad = np.asarray(item_ladder)[:n_items]
+                known = (lad >= 0) & (lad < len(ladders))
+                routed = rl > MAX_READ_LEN
+                routed[known] |= long_lad[lad[known]]
+                if routed.any():
+                    return self._cigar_routed(np.nonzero(routed)[0], ladders, packed, read_off, rl, n_items, lad, item_template,
+                                              fields, params, cap, out_ops, out_n_ops, out_status)
+        table = _ladder_args(ladders)
         rc = self.lib.tredcigar_sw_cigar(self.h, mem, *table, _ptr(packed), _ptr(read_off),
                                          _ptr(read_len), n_items, _ptr(item_ladder), _ptr(item_template), _ptr(fields),
                                          C.byref(params), cap, _ptr(out_ops), _ptr(out_n_ops), _ptr(out_status))
         if rc != 0:
             raise TredGpuError("tredcigar_sw_cigar failed ({}): {}".format(rc, self.lib.tredcigar_last_error().decode()))
 
+    @staticmethod
+    def _device_max(read_len, n):
+        """The largest of the first n read lengths of a device-memory call (a torch tensor or a raw address)."""
+        if hasattr(read_len, "data_ptr"):
+            return read_len[:n].max().item()
+        return 0                      # (a raw address: the library's own refusal of the item, TOO_LONG, stands)
+
+    def _cigar_routed(self, routed, ladders, packed, read_off, rl, n, lad, item_template, fields, params, cap, out_ops,
+                      out_n_ops, out_status):
+        """sw_cigar with the routed items through tredlong_sw_cigar and the others through tredcigar_sw_cigar, one call
+        each, merged into the caller's arrays in the caller's order (the pattern of _classify_routed)."""
+        woff = np.asarray(read_off).astype(np.int64)
+        pk = np.asarray(packed)
+        tpl = np.asarray(item_template)[:n]
+        fl = np.asarray(fields).reshape(-1, 5)[:n]
+        ops = np.asarray(out_ops).reshape(-1, cap) if cap > 0 else np.zeros((n, 0), np.uint32)
+        mask = np.zeros(n, bool)
+        mask[routed] = True
+        for sel, long_call in ((np.nonzero(~mask)[0], False), (routed, True)):
+            m = len(sel)
+            if m == 0:
+                continue
+            words = np.where((rl[sel] >= 0) & (rl[sel] <= MAX_LONG_READ_LEN), ((rl[sel] + 15) >> 4) + ((rl[sel] + 31) >> 5), 0)
+            sub_off = np.zeros(m + 1, np.int64)                     # (read_off[k] is where read k begins, in any order)
+            sub_off[1:] = np.cumsum(words)
+            sub = np.ascontiguousarray(np.concatenate([pk[woff[r]:woff[r] + w] for r, w in zip(sel, words)] +
+                                                      [np.zeros(1, pk.dtype)]), np.uint32)
+            args = [np.ascontiguousarray(rl[sel], np.int32), np.ascontiguousarray(lad[sel], np.int32),
+                    np.ascontiguousarray(tpl[sel], np.int32), np.ascontiguousarray(fl[sel], np.int16)]
+            o, no, st = np.zeros((m, cap), np.uint32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+            table = _ladder_args(ladders)
+            if long_call:
+                rc = self.lib.tredlong_sw_cigar(self.h, *table, _ptr(sub), _ptr(sub_off), _ptr(args[0]), m, _ptr(args[1]),
+                                                _ptr(args[2]), _ptr(args[3]), C.byref(params), cap, _ptr(o), _ptr(no), _ptr(st))
+                if rc != 0:
+                    raise TredGpuError("tredlong_sw_cigar failed ({}): {}".format(rc, self.lib.tredlong_last_error().decode()))
+            else:
+                rc = self.lib.tredcigar_sw_cigar(self.h, MEM_HOST, *table, _ptr(sub), _ptr(sub_off), _ptr(args[0]), m,
+                                                 _ptr(args[1]), _ptr(args[2]), _ptr(args[3]), C.byref(params), cap, _ptr(o),
+                                                 _ptr(no), _ptr(st))
+                if rc != 0:
+                    raise TredGpuError("tredcigar_sw_cigar failed ({}): {}".format(rc, self.lib.tredcigar_last_error().decode()))
+            ops[sel] = o
+            np.asarray(out_n_ops)[sel] = no
+            np.asarray(out_status)[sel] = st
+
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")
+        if self.lib.tredlong_cigar_reset_timing(self.h) != 0:
+            raise TredGpuError("tredlong_cigar_reset_timing failed: {}".format(self.lib.tredlong_last_error().decode()))
         if self.lib.tredcigar_reset_timing(self.h) != 0:
             raise TredGpuError("tredcigar_reset_timing failed: {}".format(self.lib.tredcigar_last_error().decode()))
 
@@ -510,6 +589,10 @@ class Context:
         if which == KERNEL_CIGAR:
             if self.lib.tredcigar_get_timing(self.h, C.byref(n), C.byref(ms)) != 0:
                 raise TredGpuError("tredcigar_get_timing failed: {}".format(self.lib.tredcigar_last_error().decode()))
+            return n.value, ms.value
+        if which == KERNEL_CIGAR_LONG:
+            if self.lib.tredlong_cigar_timing(self.h, C.byref(n), C.byref(ms)) != 0:
+                raise TredGpuError("tredlong_cigar_timing failed: {}".format(self.lib.tredlong_last_error().decode()))
             return n.value, ms.value
         self._chk(self.lib.tredgpu_get_timing(self.h, which, C.byref(n), C.byref(ms)), "tredgpu_get_timing")
         return n.value, ms.value
@@ -529,6 +612,7 @@ class Context:
 KERNEL_SW, KERNEL_TALLY, KERNEL_GRID = 0, 1, 2
 KERNEL_GRID_PREPARE, KERNEL_GRID_PAIRS, KERNEL_GRID_REDUCE, KERNEL_GRID_KDE = 3, 4, 5, 6
 KERNEL_CIGAR = 16               # include/tredcigar.h; tredgpu_get_timing's own series ends at 6
+KERNEL_CIGAR_LONG = 17          # tredlong_cigar_timing (include/tredlong.h): a selector of the binding's only
 
 
 def default_sw_params(clip=False, max_read_len=0):

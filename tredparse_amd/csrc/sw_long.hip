@@ -258,9 +258,11 @@ __global__ __launch_bounds__(64) void sw_long_kernel(SwArgs a, const LongLadder*
 using namespace tredgpu;
 using namespace ladder_host;
 
-namespace {
+namespace tredgpu {
+thread_local std::string g_long_error;   // the text of tredlong_last_error(); sw_cigar_long.hip writes it as well
+}
 
-thread_local std::string g_long_error;
+namespace {
 
 // device buffers of one call, released on every way out
 struct DevBufs {

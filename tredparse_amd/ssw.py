@@ -20,6 +20,16 @@ def _context():
     return _shared["ctx"]
 
 
+def set_long_reads(enabled):
+    """Switch the long-read path (Context.set_long_reads) of the shared private context: on, Aligners without a context of
+    their own take references of up to 4 095 letters and queries of up to 2 048 bp, report_cigar included."""
+    ctx = _context()
+    if not enabled and ctx.long_reads:
+        ctx.set_ladders([("N", "A", "", 0)])       # (a registered long reference would refuse the switch)
+        _shared["registered"] = None
+    ctx.set_long_reads(enabled)
+
+
 class PyAlignRes(object):
     """The reference's result object (ssw_wrap.py:259-383): the five fields, score2 = None, and -- from the operations
     `ops` (length << 4 | op, M=0 I=1 D=2; empty without report_cigar) -- its cigar_string / cigar, iter_cigar, alignment
