@@ -1,6 +1,7 @@
-"""CPU: tredparse_amd/csrc/ladder_host.h, the host code sw_long.hip and sw_cigar.hip share, through the stand-alone driver
-tests/ladder_host_main.cpp built with the address and undefined-behaviour sanitizers: the strand templates against a
-restatement in Python, the two refusals, and the scoring check at every edge of its range."""
+"""CPU: tredparse_amd/csrc/ladder_host.h, the host code sw_long.hip and the two CIGAR units share, through the stand-alone
+driver tests/ladder_host_main.cpp built with the address and undefined-behaviour sanitizers: the strand templates against a
+restatement in Python, the two refusals, the scoring check at every edge of its range, and what the CIGAR units' entry
+points take from it: the key of a ladder table, its records and letter pool, and every refusal's code and text."""
 import os
 import subprocess
 
@@ -100,3 +101,111 @@ def test_scoring_edges(run, with_flank):
         assert scoring(run, with_flank, **kw) == ("ok" if ok else text), kw
     for flank, ok in ((0, True), (-1, False), (255, True), (256, False)):
         assert scoring(run, with_flank, flank=flank) == ("ok" if ok or not with_flank else text), flank
+
+
+# ---- what the two CIGAR units share --------------------------------------------------------------------------------------
+TWO = [("ACGTTGCA", "CAG", "TGACCT", 2), ("ACNGT", "", "TGAC", 0)]     # a two-strand ladder and a plain reference
+
+
+def flat(ladders):
+    return [len(ladders)] + [x for l in ladders for x in l]
+
+
+def test_key_tells_tables_apart(run):
+    key = lambda ladders: run("K", *flat(ladders))
+    assert key(TWO) == key(list(TWO)) and key(TWO)[0].startswith("key ")
+    other = [TWO[0][:3] + (3,), TWO[1]]                                # differs in one max_units only
+    assert key(other)[0].startswith("key ") and key(other) != key(TWO)
+    assert key([TWO[0], TWO[1][:3] + (1,)]) != key(TWO)
+    assert key(TWO[:1]) != key(TWO)
+    assert key([("AC", "G", "T", 1)]) != key([("A", "CG", "T", 1)])    # the parts are kept apart
+    assert run("K", 2, *TWO[0], "ACGT", "NULL", "TGAC", 1) == ["refused -2 ladder 1: NULL sequence"]
+    assert run("K", 1, "NULL", "CAG", "TGAC", 1) == ["refused -2 ladder 0: NULL sequence"]
+    assert run("K", 1, "ACGT", "CAG", "NULL", 1) == ["refused -2 ladder 0: NULL sequence"]
+
+
+def expected_pool(ladders):
+    """The records and the pool as the restatement gives them: per ladder and strand the trunk, then the branch."""
+    pool, lines = "", []
+    for l in ladders:
+        strands = [x.split("\t") for x in expected(*l)[1:]]
+        lines.append("{}\t{}".format(len(l[1]), l[3]))
+        for alen, blen, trunk, branch in strands:
+            lines.append("{}\t{}\t{}\t{}".format(alen, blen, len(pool), len(pool) + len(trunk)))
+            pool += trunk + branch
+        lines += ["0\t0\t0\t0"] * (2 - len(strands))                  # a plain reference has no second strand
+    return ["pool " + pool + "N" * 16] + lines
+
+
+@pytest.mark.parametrize("ladders", [TWO, TWO[::-1], TWO[:1], TWO[1:], [LADDERS[6]], LADDERS])
+def test_pool_equals_the_restatement(run, ladders):
+    assert run("P", 0, *flat(ladders)) == expected_pool(ladders)
+
+
+def test_pack_refusals(run):
+    long_one = ("A" * 2048, "C", "G" * 2047, 1)                        # its longest template has 4 096 letters
+    text = "refused -2 ladder 1: longest template 4096 exceeds TREDGPU_MAX_LONG_TEMPLATE_LEN=4095"
+    assert run("P", 4095, *flat([TWO[0], long_one])) == [text]
+    assert run("P", 4096, *flat([TWO[0], long_one])) == expected_pool([TWO[0], long_one])
+    assert run("P", 0, *flat([TWO[0], long_one])) == expected_pool([TWO[0], long_one])      # 0: no limit
+    assert run("P", 4095, *flat([("A" * 4096, "", "", 0)])) == ["refused -2 ladder 0: longest template 4096 exceeds "
+                                                                "TREDGPU_MAX_LONG_TEMPLATE_LEN=4095"]
+    assert run("P", 0, *flat([TWO[0], ("ACGT", "", "TGAC", 2)])) == ["refused -2 ladder 1: empty repeat"]
+    assert run("P", 0, *flat([("ACGT", "CAG", "TGAC", -1)])) == ["refused -2 ladder 0: negative max_units"]
+
+
+ARGS_TEXT = "n_items, n_ladders and cap must be positive"
+GOOD_CALL = dict(ctx=1, mem_ok=1, n_items=1, n_ladders=1, cap=8, null_table=0, params="1,5,7,2", null_array=-1)
+CALLS = [    # in the order of the checks: an earlier one wins
+    (dict(), 0, ""),
+    (dict(n_items=0, null_array=0), 0, ""),                             # no items: the arrays are not looked at
+    (dict(n_items=0x7fffffff), 0, ""),
+    (dict(ctx=0, mem_ok=0, n_items=-1), -2, "ctx is NULL"),
+    (dict(mem_ok=0, n_items=-1), -2, "mem must be TREDGPU_MEM_HOST or TREDGPU_MEM_DEVICE"),
+    (dict(n_items=-1, null_table=1), -2, ARGS_TEXT),
+    (dict(n_items=0x80000000), -2, ARGS_TEXT),
+    (dict(n_ladders=0), -2, ARGS_TEXT),
+    (dict(n_ladders=-1), -2, ARGS_TEXT),
+    (dict(cap=0, params="NULL"), -2, ARGS_TEXT),
+    (dict(null_table=1, params="NULL"), -2, "NULL ladder argument"),
+    (dict(null_table=2), -2, "NULL ladder argument"),
+    (dict(null_table=3), -2, "NULL ladder argument"),
+    (dict(null_table=4), -2, "NULL ladder argument"),
+    (dict(params="NULL", null_array=0), -2, "params is NULL"),
+    (dict(params="0,5,7,2", null_array=0), -2, CIGAR_TEXT),
+    (dict(params="1,5,7,8"), -2, CIGAR_TEXT),
+] + [(dict(null_array=k), -2, "NULL array argument") for k in range(9)]
+
+
+@pytest.mark.parametrize("kw,rc,text", CALLS)
+def test_call_refusals(run, kw, rc, text):
+    c = dict(GOOD_CALL, **kw)
+    out = run("C", c["ctx"], c["mem_ok"], c["n_items"], c["n_ladders"], c["cap"], c["null_table"], c["params"], c["null_array"])
+    assert out == ["call {} {}".format(rc, text)]
+
+
+INSIDE = "item {}: its read does not lie inside packed[0 .. read_off[n_items])"
+READS = [    # max_read, read_off (n + 1), read_len (n): a read of L letters has (L + 15) // 16 + (L + 31) // 32 words
+    (2048, [0, 3], [20], 0, ""),
+    (2048, [0, 2], [20], -2, INSIDE.format(0)),
+    (2048, [3, 0], [20], -2, "read_off must be monotone"),
+    (2048, [-1, 3], [20], -2, "read_off must be monotone"),
+    (-1, [3, 0], [20], -2, "read_off must be monotone"),
+    (-1, [0, 2], [20], 0, ""),                                          # max_read < 0: the reads are not looked at
+    (-1, [5, 5], [20], 0, ""),
+    (2048, [0, 3, 6], [20, 33], -2, INSIDE.format(1)),                  # 33 letters: 3 + 2 words
+    (2048, [0, 3, 8], [20, 33], 0, ""),
+    (2048, [0, 5, 8], [20, 20], 0, ""),                                 # the offsets say where a read begins, in any order
+    (2048, [5, 0, 8], [20, 20], 0, ""),
+    (2048, [0, -1, 8], [20, 20], -2, INSIDE.format(1)),
+    (2048, [0, 0, 0], [0, 0], 0, ""),                                   # an empty read has no words
+    (2048, [0, 0, 2], [-1, 2049], 0, ""),                               # reads the kernel refuses are not read
+    (2048, [0, 0, 2], [0, 2048], -2, INSIDE.format(1)),
+    (2048, [0, 0, 192], [0, 2048], 0, ""),                              # 128 + 64 words
+    (480, [0, 0, 2], [0, 481], 0, ""),
+]
+
+
+@pytest.mark.parametrize("max_read,off,length,rc,text", READS)
+def test_reads_refusals(run, max_read, off, length, rc, text):
+    assert run("R", max_read, len(length), *off, *length) == ["reads {} {}".format(rc, text)]

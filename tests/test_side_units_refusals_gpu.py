@@ -1,6 +1,7 @@
 """GPU: what the two opt-in units (include/tredlong.h, include/tredcigar.h) refuse in host code before any launch, called
 through ctx.lib directly: the return code together with the whole *_last_error() text.  The long path is called with
-n_reads = 0 (its ladder table is checked, no kernel runs); the CIGAR unit with one 20 bp item."""
+n_reads = 0 (its ladder table is checked, no kernel runs); the two CIGAR units with one 20 bp item, which also pins what
+their shared host code owns: a usable unit after every refusal, the fold of the event pool, and release twice over."""
 import ctypes as C
 
 import numpy as np
@@ -53,21 +54,36 @@ def _rc(s):
     return s[::-1].translate(str.maketrans("ACGT", "TGCA"))
 
 
-def _cigar(ctx, ladder, p=None):
-    """One item: the first 20 letters of LADDER's one-unit template of the reverse strand, against that template."""
+def _one_item(ctx, unit, ladder=LADDER, p=None, **over):
+    """One item on unit "cigar" or "long": the first 20 letters of LADDER's one-unit template of the reverse strand, against
+    that template.  over replaces arguments of the entry point by name (a missing pointer is None; scoring: fields of the
+    parameters)."""
     pre, rep, suf, _ = LADDER
     read = (_rc(suf) + _rc(rep) + _rc(pre))[:20]
     packed, woff, rlen = _lib.pack_reads([read])
-    n, pres, reps, sufs, mu = _table([ladder])
-    fields = np.array([[20, 0, 19, 0, 19]], np.int16)
-    item_ladder, item_template = np.zeros(1, np.int32), np.ones(1, np.int32)
-    cap = 8
-    ops, n_ops, status = np.full((1, cap), 7, np.uint32), np.full(1, -1, np.int32), np.full(1, -1, np.int32)
-    p = p or _lib.default_sw_params()
-    rc = ctx.lib.tredcigar_sw_cigar(ctx.h, _lib.MEM_HOST, n, pres, reps, sufs, _lib._ptr(mu), _lib._ptr(packed),
-                                    _lib._ptr(woff), _lib._ptr(rlen), 1, _lib._ptr(item_ladder), _lib._ptr(item_template),
-                                    _lib._ptr(fields), C.byref(p), cap, _lib._ptr(ops), _lib._ptr(n_ops), _lib._ptr(status))
-    return rc, ctx.lib.tredcigar_last_error().decode(), (int(status[0]), list(ops[0, :max(int(n_ops[0]), 0)]))
+    cap = over.get("cap", 8)
+    if "scoring" in over:
+        p = _params(**over.pop("scoring"))
+    ops, n_ops, status = np.full((1, max(cap, 1)), 7, np.uint32), np.full(1, -1, np.int32), np.full(1, -1, np.int32)
+    a = dict(prefix=(C.c_char_p * 1)(None if ladder[0] is None else ladder[0].encode()),
+             repeat=(C.c_char_p * 1)(ladder[1].encode()), suffix=(C.c_char_p * 1)(ladder[2].encode()),
+             max_units=np.asarray([ladder[3]], np.int32), packed=packed, read_off=woff, read_len=rlen, n_items=1,
+             item_ladder=np.zeros(1, np.int32), item_template=np.ones(1, np.int32),
+             fields=np.array([[20, 0, 19, 0, 19]], np.int16), params=p or _lib.default_sw_params(), cap=cap, out_ops=ops,
+             out_n_ops=n_ops, out_status=status, mem=_lib.MEM_HOST)
+    a.update(over)
+    head = (ctx.h,) if unit == "long" else (ctx.h, a["mem"])
+    call = ctx.lib.tredlong_sw_cigar if unit == "long" else ctx.lib.tredcigar_sw_cigar
+    rc = call(*head, 1, a["prefix"], a["repeat"], a["suffix"], _lib._ptr(a["max_units"]), _lib._ptr(a["packed"]),
+              _lib._ptr(a["read_off"]), _lib._ptr(a["read_len"]), a["n_items"], _lib._ptr(a["item_ladder"]),
+              _lib._ptr(a["item_template"]), _lib._ptr(a["fields"]), None if a["params"] is None else C.byref(a["params"]),
+              a["cap"], _lib._ptr(a["out_ops"]), _lib._ptr(a["out_n_ops"]), _lib._ptr(a["out_status"]))
+    err = (ctx.lib.tredlong_last_error if unit == "long" else ctx.lib.tredcigar_last_error)().decode()
+    return rc, err, (int(status[0]), list(ops[0, :max(int(n_ops[0]), 0)]))
+
+
+def _cigar(ctx, ladder, p=None):
+    return _one_item(ctx, "cigar", ladder, p)
 
 
 GOOD = (0, "", (_lib.CIGAR_OK, [20 << 4]))
@@ -97,3 +113,60 @@ def test_each_unit_reports_its_own_error(ctx):
     assert _long(ctx, LADDER) == (0, "")
     assert _cigar(ctx, ("ACGT", "CAG", "TTGA", -1))[1] == "ladder 0: negative max_units"
     assert ctx.lib.tredlong_last_error() == b""
+
+
+ARGS = "n_items, n_ladders and cap must be positive"
+COMMON_REFUSALS = [      # the checks both entry points make, in their order
+    (dict(n_items=-1), ARGS),
+    (dict(cap=0), ARGS),
+    (dict(repeat=None), "NULL ladder argument"),
+    (dict(params=None), "params is NULL"),
+    (dict(out_n_ops=None), "NULL array argument"),
+    (dict(ladder=(None, "CAG", "TGACCTAGGT", 3)), "ladder 0: NULL sequence"),
+    (dict(scoring=dict(gap_open=17)), CIGAR_SCORING),
+    (dict(read_off=np.array([3, 0], np.int64)), "read_off must be monotone"),
+]
+
+
+@pytest.mark.parametrize("over,text", COMMON_REFUSALS + [
+    (dict(read_off=np.array([0, 2], np.int64)), "item 0: its read does not lie inside packed[0 .. read_off[n_items])"),
+    (dict(ladder=("A" * 2048, "C", "G" * 2047, 1)),
+     "ladder 0: longest template 4096 exceeds TREDGPU_MAX_LONG_TEMPLATE_LEN=4095"),
+])
+def test_long_cigar_refusals_leave_the_unit_usable(ctx, over, text):
+    assert _one_item(ctx, "long") == GOOD
+    rc, err, _ = _one_item(ctx, "long", **over)
+    assert (rc, err) == (-2, text)
+    assert _one_item(ctx, "long") == GOOD
+
+
+@pytest.mark.parametrize("over,text", COMMON_REFUSALS + [
+    (dict(mem=2), "mem must be TREDGPU_MEM_HOST or TREDGPU_MEM_DEVICE"),
+])
+def test_cigar_argument_refusals_leave_the_unit_usable(ctx, over, text):
+    assert _one_item(ctx, "cigar") == GOOD
+    rc, err, _ = _one_item(ctx, "cigar", **over)
+    assert (rc, err) == (-2, text)
+    assert _one_item(ctx, "cigar") == GOOD
+
+
+@pytest.mark.parametrize("unit,which", [("cigar", _lib.KERNEL_CIGAR), ("long", _lib.KERNEL_CIGAR_LONG)])
+def test_event_pool_folds_beyond_256_calls(ctx, unit, which):
+    """One event pair per call and 256 pairs held at the most: call 257 folds the finished ones into the totals."""
+    ctx.reset_timing()
+    for _ in range(260):
+        assert _one_item(ctx, unit) == GOOD
+    launches, ms = ctx.get_timing(which)
+    assert launches == 260 and ms > 0
+    assert ctx.get_timing(which) == (260, ms)               # nothing is counted twice
+    ctx.reset_timing()
+    assert ctx.get_timing(which) == (0, 0.0)
+
+
+@pytest.mark.parametrize("unit", ["cigar", "long"])
+def test_release_twice_then_a_good_call(ctx, unit):
+    release = ctx.lib.tredlong_release if unit == "long" else ctx.lib.tredcigar_release
+    assert _one_item(ctx, unit) == GOOD
+    release(ctx.h)
+    release(ctx.h)
+    assert _one_item(ctx, unit) == GOOD

@@ -363,8 +363,7 @@ class Context:
         sub_len = np.ascontiguousarray(rl[routed])      # (held here: _ptr keeps no reference)
         rc = self.lib.tredlong_sw_classify(self.h, *table, _ptr(sub), _ptr(sub_off), _ptr(sub_len), m, _ptr(lad), C.byref(p),
                                            _ptr(tag), _ptr(h), _ptr(sc), _ptr(dump), dump_templates if dump is not None else 0)
-        if rc != 0:
-            raise TredGpuError("tredlong_sw_classify failed ({}): {}".format(rc, self.lib.tredlong_last_error().decode()))
+        self._chk_side(rc, "tredlong_sw_classify failed ({})".format(rc), self.lib.tredlong_last_error)
         np.asarray(out_tag)[routed] = tag
         np.asarray(out_h)[routed] = h
         np.asarray(out_score)[routed] = sc
@@ -523,12 +522,25 @@ class Context:
                 if routed.any():
                     return self._cigar_routed(np.nonzero(routed)[0], ladders, packed, read_off, rl, n_items, lad, item_template,
                                               fields, params, cap, out_ops, out_n_ops, out_status)
+        self._cigar_call(False, mem, ladders, packed, read_off, read_len, n_items, item_ladder, item_template, fields, params,
+                         cap, out_ops, out_n_ops, out_status)
+
+    def _cigar_call(self, long_call, mem, ladders, packed, read_off, read_len, n_items, item_ladder, item_template, fields,
+                    params, cap, out_ops, out_n_ops, out_status):
+        """One call of tredlong_sw_cigar (long_call; host memory only, so it has no mem argument) or tredcigar_sw_cigar."""
+        name = "tredlong_sw_cigar" if long_call else "tredcigar_sw_cigar"
         table = _ladder_args(ladders)
-        rc = self.lib.tredcigar_sw_cigar(self.h, mem, *table, _ptr(packed), _ptr(read_off),
-                                         _ptr(read_len), n_items, _ptr(item_ladder), _ptr(item_template), _ptr(fields),
-                                         C.byref(params), cap, _ptr(out_ops), _ptr(out_n_ops), _ptr(out_status))
+        rc = getattr(self.lib, name)(self.h, *(() if long_call else (mem,)), *table, _ptr(packed), _ptr(read_off),
+                                     _ptr(read_len), n_items, _ptr(item_ladder), _ptr(item_template), _ptr(fields),
+                                     C.byref(params), cap, _ptr(out_ops), _ptr(out_n_ops), _ptr(out_status))
+        self._chk_side(rc, "{} failed ({})".format(name, rc),
+                       self.lib.tredlong_last_error if long_call else self.lib.tredcigar_last_error)
+
+    @staticmethod
+    def _chk_side(rc, what, last_error):
+        """Raises a side unit's error with the text of its own last_error (tredlong_* / tredcigar_*), not the context's."""
         if rc != 0:
-            raise TredGpuError("tredcigar_sw_cigar failed ({}): {}".format(rc, self.lib.tredcigar_last_error().decode()))
+            raise TredGpuError("{}: {}".format(what, last_error().decode()))
 
     @staticmethod
     def _device_max(read_len, n):
@@ -560,39 +572,28 @@ class Context:
             args = [np.ascontiguousarray(rl[sel], np.int32), np.ascontiguousarray(lad[sel], np.int32),
                     np.ascontiguousarray(tpl[sel], np.int32), np.ascontiguousarray(fl[sel], np.int16)]
             o, no, st = np.zeros((m, cap), np.uint32), np.zeros(m, np.int32), np.zeros(m, np.int32)
-            table = _ladder_args(ladders)
-            if long_call:
-                rc = self.lib.tredlong_sw_cigar(self.h, *table, _ptr(sub), _ptr(sub_off), _ptr(args[0]), m, _ptr(args[1]),
-                                                _ptr(args[2]), _ptr(args[3]), C.byref(params), cap, _ptr(o), _ptr(no), _ptr(st))
-                if rc != 0:
-                    raise TredGpuError("tredlong_sw_cigar failed ({}): {}".format(rc, self.lib.tredlong_last_error().decode()))
-            else:
-                rc = self.lib.tredcigar_sw_cigar(self.h, MEM_HOST, *table, _ptr(sub), _ptr(sub_off), _ptr(args[0]), m,
-                                                 _ptr(args[1]), _ptr(args[2]), _ptr(args[3]), C.byref(params), cap, _ptr(o),
-                                                 _ptr(no), _ptr(st))
-                if rc != 0:
-                    raise TredGpuError("tredcigar_sw_cigar failed ({}): {}".format(rc, self.lib.tredcigar_last_error().decode()))
+            self._cigar_call(long_call, MEM_HOST, ladders, sub, sub_off, args[0], m, args[1], args[2], args[3], params, cap, o, no,
+                             st)
             ops[sel] = o
             np.asarray(out_n_ops)[sel] = no
             np.asarray(out_status)[sel] = st
 
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")
-        if self.lib.tredlong_cigar_reset_timing(self.h) != 0:
-            raise TredGpuError("tredlong_cigar_reset_timing failed: {}".format(self.lib.tredlong_last_error().decode()))
-        if self.lib.tredcigar_reset_timing(self.h) != 0:
-            raise TredGpuError("tredcigar_reset_timing failed: {}".format(self.lib.tredcigar_last_error().decode()))
+        self._chk_side(self.lib.tredlong_cigar_reset_timing(self.h), "tredlong_cigar_reset_timing failed",
+                       self.lib.tredlong_last_error)
+        self._chk_side(self.lib.tredcigar_reset_timing(self.h), "tredcigar_reset_timing failed", self.lib.tredcigar_last_error)
 
     def get_timing(self, which):
         """(launches, total device ms) of kernel `which` since reset_timing (HIP events)."""
         n, ms = C.c_int64(0), C.c_double(0)
         if which == KERNEL_CIGAR:
-            if self.lib.tredcigar_get_timing(self.h, C.byref(n), C.byref(ms)) != 0:
-                raise TredGpuError("tredcigar_get_timing failed: {}".format(self.lib.tredcigar_last_error().decode()))
+            self._chk_side(self.lib.tredcigar_get_timing(self.h, C.byref(n), C.byref(ms)), "tredcigar_get_timing failed",
+                           self.lib.tredcigar_last_error)
             return n.value, ms.value
         if which == KERNEL_CIGAR_LONG:
-            if self.lib.tredlong_cigar_timing(self.h, C.byref(n), C.byref(ms)) != 0:
-                raise TredGpuError("tredlong_cigar_timing failed: {}".format(self.lib.tredlong_last_error().decode()))
+            self._chk_side(self.lib.tredlong_cigar_timing(self.h, C.byref(n), C.byref(ms)), "tredlong_cigar_timing failed",
+                           self.lib.tredlong_last_error)
             return n.value, ms.value
         self._chk(self.lib.tredgpu_get_timing(self.h, which, C.byref(n), C.byref(ms)), "tredgpu_get_timing")
         return n.value, ms.value

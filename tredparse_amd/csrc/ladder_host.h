@@ -1,5 +1,7 @@
-// ladder_host.h -- the host code the two opt-in units (sw_long.hip, sw_cigar.hip) share: base codes, the strand templates
-// of a ladder, the error-text helper and the scoring-range check.  Plain C++17, nothing from HIP.
+// ladder_host.h -- the host code the opt-in units (sw_long.hip, and through cigar_unit.h sw_cigar.hip and
+// sw_cigar_long.hip) share: base codes, the strand templates of a ladder, the error-text helper and the scoring-range
+// check; for the two CIGAR units also the key of a ladder table, its packing into records and a letter pool, and the
+// argument checks of their entry points.  Plain C++17, nothing from HIP (tests/ladder_host_main.cpp runs it under ASan).
 //
 // capi.hip keeps its own copy of these functions (base_code / encode / revcomp and the construction in
 // tredgpu_set_ladders) on purpose: it belongs to the sources whose hash the records under profiles/ carry (SRC_HASH in
@@ -8,6 +10,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -98,6 +101,87 @@ inline const char* scoring_refusal(const tredgpu_sw_params& p, bool with_flank) 
     return with_flank ? "scoring out of the supported range (match 1..8, mismatch 0..16, "
                         "1 <= gap_extend <= gap_open <= 16, flank 0..255)"
                       : "scoring out of the supported range (match 1..8, mismatch 0..16, 1 <= gap_extend <= gap_open <= 16)";
+}
+
+// ---- what the two CIGAR units (cigar_unit.h) share ---------------------------------------------------------------------
+
+// a ladder table as the entry points take it
+struct Table { int32_t n; const char* const *prefix, *const *repeat, *const *suffix; const int32_t* max_units; };
+
+// one ladder of a packed table: strand s has its trunk at letters[trunk_off[s]] and its branch at letters[branch_off[s]]
+struct LadderRecord {
+    int32_t alen[2], blen[2];
+    int32_t trunk_off[2], branch_off[2];   // byte offsets into the letter pool (one code 0..4 per byte)
+    int32_t period, max_units;
+};
+
+// the text two tables share only when they are the same table; refuses a NULL sequence
+inline int ladder_key(std::string& err, const Table& t, std::string& key) {
+    key.clear();
+    for (int i = 0; i < t.n; ++i) {
+        if (!t.prefix[i] || !t.repeat[i] || !t.suffix[i]) return fail(err, -2, "ladder %d: NULL sequence", i);
+        key += t.prefix[i]; key += '|'; key += t.repeat[i]; key += '|'; key += t.suffix[i]; key += '|';
+        key += std::to_string(t.max_units[i]); key += ';';
+    }
+    return 0;
+}
+
+// the table as records and one pool of letters: per ladder and strand the trunk, then the branch, and 16 bytes of N behind
+// the last.  max_template: the longest template a ladder may have (0: the items are checked on the device instead)
+inline int pack_ladders(std::string& err, const Table& t, int max_template, std::vector<LadderRecord>& lad, Codes& pool) {
+    lad.assign((size_t)t.n, LadderRecord());
+    pool.clear();
+    auto append = [&pool](const Codes& v) {
+        const int off = (int)pool.size();
+        pool.insert(pool.end(), v.begin(), v.end());
+        return off;
+    };
+    Strands S;
+    for (int i = 0; i < t.n; ++i) {
+        LadderRecord& d = lad[i];
+        if (const char* why = build_strands(t.prefix[i], t.repeat[i], t.suffix[i], t.max_units[i], S))
+            return fail(err, -2, "ladder %d: %s", i, why);
+        const size_t T = (size_t)S.alen[0] + S.blen[0] + (size_t)S.period * S.max_units;
+        if (max_template > 0 && T > (size_t)max_template)
+            return fail(err, -2, "ladder %d: longest template %zu exceeds TREDGPU_MAX_LONG_TEMPLATE_LEN=%d", i, T, max_template);
+        d.period = S.period; d.max_units = S.max_units;
+        for (int k = 0; k < S.n_strands; ++k) {
+            d.alen[k] = S.alen[k];
+            d.blen[k] = S.blen[k];
+            d.trunk_off[k] = append(S.trunk[k]);
+            d.branch_off[k] = append(S.branch[k]);
+        }
+    }
+    pool.resize(pool.size() + 16, 4);
+    return 0;
+}
+
+// what an entry point refuses before it reads an array.  mem_ok: the unit's own check of its memory switch; arrays: the
+// nine of the items, looked at only when there are items
+inline int call_refusal(std::string& err, const void* ctx, bool mem_ok, const Table& t, int64_t n_items, int32_t cap,
+                        const tredgpu_sw_params* p, std::initializer_list<const void*> arrays) {
+    if (!ctx) return fail(err, -2, "ctx is NULL");
+    if (!mem_ok) return fail(err, -2, "mem must be TREDGPU_MEM_HOST or TREDGPU_MEM_DEVICE");
+    if (n_items < 0 || n_items > 0x7fffffff || t.n <= 0 || cap <= 0) return fail(err, -2, "n_items, n_ladders and cap must be positive");
+    if (!t.prefix || !t.repeat || !t.suffix || !t.max_units) return fail(err, -2, "NULL ladder argument");
+    if (!p) return fail(err, -2, "params is NULL");
+    if (const char* why = scoring_refusal(*p, false)) return fail(err, -2, "%s", why);
+    for (const void* a : arrays)
+        if (n_items > 0 && !a) return fail(err, -2, "NULL array argument");
+    return 0;
+}
+
+// host memory: packed[0 .. read_off[n]) is what a call copies to the device.  With max_read >= 0 the words of every read
+// the kernel accepts (0 <= L <= max_read) must be among them, since it reads them
+inline int reads_refusal(std::string& err, const int64_t* read_off, const int32_t* read_len, size_t n, int max_read) {
+    if (read_off[0] < 0 || read_off[n] < read_off[0]) return fail(err, -2, "read_off must be monotone");
+    for (size_t k = 0; k < n && max_read >= 0; ++k) {
+        const int L = read_len[k];
+        if (L < 0 || L > max_read) continue;
+        if (read_off[k] < 0 || read_off[k] + ((L + 15) >> 4) + ((L + 31) >> 5) > read_off[n])
+            return fail(err, -2, "item %zu: its read does not lie inside packed[0 .. read_off[n_items])", k);
+    }
+    return 0;
 }
 
 }  // namespace ladder_host
