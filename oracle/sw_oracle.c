@@ -125,8 +125,8 @@ int oracle_sw_align(const int8_t* read, int L, const int8_t* ref, int T,
     dp_sweep(read, L, ref, 0, 1, T, match, mismatch, go, ge, -1, &score, &ref_end, &read_end);
     /* reverse pass: reversed read[0..read_end] against ref[ref_end..0], stop at first column
        whose max equals the forward score (ssw.c:839-846) */
-    int n = read_end + 1;
-    int8_t* rev = (int8_t*)malloc((size_t)n);
+    int n = L > 0 ? read_end + 1 : 0;   /* an empty read has no row 0 to reverse */
+    int8_t* rev = (int8_t*)malloc((size_t)n + 1);
     for (int i = 0; i < n; i++) rev[i] = read[read_end - i];
     int s2, ref_begin, rrow;
     dp_sweep(rev, n, ref, ref_end, -1, ref_end + 1, match, mismatch, go, ge, score,

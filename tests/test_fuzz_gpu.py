@@ -9,6 +9,9 @@ re-draws them: the long campaigns logged under profiles/ are the same code with 
   fuzz_grid       SW -> histograms -> grid on random synthetic batches vs the numpy oracle
   fuzz_cigar      the CIGAR kernel vs the reference's own compiled banded_sw (oracle/_ref; without it tests/cigar_model.py,
                   which tests/test_cigar_model.py pins to the reference) pair by pair at six scorings: every operation
+  fuzz_long       the long-read kernel vs the C restatement (tests/test_oracle_sw.py pins it to the reference on long pairs
+                  at these scorings) at ten scorings, the three row classes mixed in every call: (tag, h, score) per read
+                  and every template's dump row
 """
 import os
 import sys
@@ -63,3 +66,15 @@ def test_fuzz_cigar_slice():
     assert res["compared"] >= 0.9 * res["pairs"] == 1350, res
     assert 2 * res["with_gap"] > res["compared"], res
     assert res["wide_tier"] >= 1, res
+
+
+def test_fuzz_long_slice():
+    """Ten rounds meet each of the ten scorings once.  The oracle side is the cost: 33 s of the 34 on 16 threads (64 s on
+    8); the GPU's share is under a second."""
+    import fuzz_long
+    res = fuzz_long.campaign(rounds=10, seed=20270307)
+    print(res)
+    assert res["reads"] > 300 and res["template_pairs"] > 50000, res
+    assert sorted(res["scorings"]) == sorted("/".join(map(str, s)) for s in fuzz_long.SCORINGS), res
+    assert min(res["class8"], res["class16"], res["class32"]) >= 50, res
+    assert res["mismatches"] == 0 and res["pair_mismatches"] == 0, res

@@ -99,6 +99,92 @@ def test_oracle_matches_compiled_reference_random():
         assert np.array_equal(got[k], want[k]), k
 
 
+# the scorings the long-read kernel's GPU tests run (tools/fuzz_long.py, tests/test_long_sw_shapes_gpu.py) beyond the three
+# pinned above; the last three are corners of the range the kernels accept
+LONG_SCORINGS = ((1, 1, 2, 1), (3, 5, 7, 2), (1, 0, 1, 1), (1, 9, 12, 3), (8, 16, 16, 16), (8, 0, 1, 1), (1, 16, 16, 1))
+LONG_SEED = 20270308
+HD = ("GAGTCCCTCAAGTCCTTC", "CAG", "CAACAGCCGCCACCGCCG")      # tredparse_amd/data/treds.json
+
+
+def long_pairs(k):
+    """Eight long (read, template) pairs for LONG_SCORINGS[k]: reads of 513 and 1 025 letters against HD templates of
+    600 ... 4 095 columns on either strand.  Suffix, prefix and inside-repeat reads with a few errors, a pure repeat, a
+    two-letter read (many cells share the best score), a read with N runs and a random one."""
+    rng = np.random.default_rng(LONG_SEED + k)
+    pre, rep, suf = HD
+    rnd = lambda n: "".join("ACGT"[i] for i in rng.integers(0, 4, n))
+    reads, refs = [], []
+    cols = [int(c) for c in rng.permutation([600, 700, 1000, 1400, 2047, 2048, 3000, 4095])]
+    for j, kind in enumerate(("suffix", "prefix", "inside", "pure", "two", "nruns", "random", "suffix")):
+        L = (513, 1025)[j % 2]
+        units = (cols[j] - len(pre) - len(suf)) // 3
+        t = pre + rep * units + suf
+        assert 600 <= len(t) <= 4095
+        g = rnd(L) + t + rnd(L)
+        if kind in ("suffix", "prefix", "inside", "nruns"):
+            a = {"suffix": L + len(t) - L // 3, "prefix": L // 3, "inside": L + len(pre) + 4,
+                 "nruns": L + int(rng.integers(0, len(t) - L // 2))}[kind]
+            r = list(g[a:a + L])
+            for i in rng.integers(0, L, L // 100):
+                r[i] = "ACGT"[int(rng.integers(4))]
+            if kind == "nruns":
+                for i in rng.integers(0, L - 30, 3):
+                    r[i:i + 30] = "N" * 30
+            r = "".join(r)
+        elif kind == "pure":
+            r = (rep * L)[1:L + 1]
+        elif kind == "two":
+            r = "".join("AG"[i] for i in rng.integers(0, 2, L))
+        else:
+            r = rnd(L)
+        assert len(r) == L
+        turn = bool(rng.integers(2))
+        reads.append(po.rc(r) if turn else r)
+        refs.append(po.rc(t) if j % 3 == 2 else t)
+    return reads, refs
+
+
+def long_answers(sw_pairs, scorings=LONG_SCORINGS):
+    """{scoring: (score, ref_begin, ref_end, read_begin, read_end) per pair of long_pairs} by sw_pairs (po.sw_pairs or
+    po.ref_sw_pairs).  tools/gen_golden.py stores the reference's in tests/golden/sw_long_pairs.npz."""
+    out = {}
+    for k, scoring in enumerate(LONG_SCORINGS):
+        if scoring in scorings:
+            reads, refs = long_pairs(k)
+            out["scoring_" + "_".join(map(str, scoring))] = sw_pairs(reads, refs, list(range(8)), list(range(8)), scoring=scoring,
+                                                                      threads=8)
+    return out
+
+
+def test_oracle_matches_compiled_reference_long_pairs():
+    """The restatement against the compiled reference on long pairs at the seven scorings that only the long-read kernel's
+    GPU tests use, where those tests lean on the restatement alone: the stored answers (tests/golden/sw_long_pairs.npz),
+    and -- where oracle/_ref is built -- the live ones, which must still be the stored ones.  A pair on which the
+    reference's CIGAR pass faults (REF_CRASHED) is left out; at most a quarter of a scoring's pairs may be.
+
+    gap_open == gap_extend: the reference's 16-bit pass leaves its lazy-F loop one row early there (ssw.c:472-477: once
+    the loop has raised H(i) to F, `F - gap_extend > H(i) - gap_open` is false and it stops, so the vertical gap never
+    reaches row i + 1 across a segment boundary), its 8-bit pass tests the next row and does not.  A truncated F only ever
+    lowers cells, so at those scorings the reference's score may fall short of the recurrence's, never exceed it: such a
+    pair counts as left out as well, within the same quarter (stored: one pair of eight at 8/0/1/1, 2 665 against 2 667;
+    none at 1/0/1/1 and 8/16/16/16).  The kernels and this restatement compute the recurrence in full."""
+    want = dict(np.load(os.path.join(GOLD, "sw_long_pairs.npz")))
+    assert set(want) == {"scoring_" + "_".join(map(str, s)) for s in LONG_SCORINGS}
+    if po.have_ref():
+        live = long_answers(po.ref_sw_pairs)
+        assert set(live) == set(want) and all(np.array_equal(live[k], want[k]) for k in want)
+    got = long_answers(po.sw_pairs)
+    for scoring in LONG_SCORINGS:
+        k = "scoring_" + "_".join(map(str, scoring))
+        ok = want[k][:, 0] != po.REF_CRASHED
+        if scoring[2] == scoring[3]:
+            ok &= want[k][:, 0] >= got[k][:, 0]
+        print(k, "left out:", int((~ok).sum()), "of", len(ok))
+        assert want[k].shape == (8, 5) and (~ok).sum() <= 2, k
+        assert (want[k][ok, 0] >= 255).any(), k        # the reference's 16-bit pass took part
+        assert np.array_equal(got[k][ok], want[k][ok]), (k, got[k], want[k])
+
+
 # tools/fuzz_parity.py seed 20271201, round 334: a 300-base (CTG)n read with a few errors against the DM1 ladder
 FAULT_READ = ("TGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCCGCTGCTGCT"
               "GCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTGCTG"

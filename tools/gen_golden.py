@@ -12,6 +12,7 @@ The outputs are plain data (inputs + expected outputs); no reference source is s
   kde.npz          global_lens -> PEMaxLikModel.pdf
   sw_random.npz    the compiled reference ssw.c's answers to tests/test_oracle_sw.py's random pairs (random_answers)
   sw_fault.npz     its answers to the (CTG)n read its CIGAR pass faults on (tests/test_oracle_sw.py fault_answers)
+  sw_long_pairs.npz  its answers to long pairs at the scorings of the long-read kernel's tests (long_answers)
 """
 import json
 import logging
@@ -737,10 +738,11 @@ def gen_debug(loci):
 
 
 def gen_sw_ref():
-    """sw_random.npz / sw_fault.npz: the inputs are tests/test_oracle_sw.py's, only the reference's answers are stored."""
+    """sw_random.npz / sw_fault.npz / sw_long_pairs.npz: the inputs are tests/test_oracle_sw.py's, only the reference's answers are stored."""
     from tests import test_oracle_sw as t
     np.savez_compressed(os.path.join(GOLD, "sw_random.npz"), **t.random_answers(po.ref_sw_pairs))
     np.savez_compressed(os.path.join(GOLD, "sw_fault.npz"), **t.fault_answers(po.ref_classify, po.ref_sw_pairs))
+    np.savez_compressed(os.path.join(GOLD, "sw_long_pairs.npz"), **t.long_answers(po.ref_sw_pairs))
 
 
 def main():

@@ -345,10 +345,13 @@ class Context:
         masked[routed] = 0
         p = SwParams(params.match, params.mismatch, params.gap_open, params.gap_extend, params.flank, params.clip,
                      min(int(params.max_read_len), MAX_READ_LEN), params.reserved)
-        self._chk(self.lib.tredgpu_sw_classify(self.h, MEM_HOST, _ptr(packed), _ptr(read_off), _ptr(masked), n_reads,
-                                               _ptr(unit_read_off), _ptr(unit_ladder), n_units, C.byref(p), _ptr(out_tag),
-                                               _ptr(out_h), _ptr(out_score), _ptr(out_dump), dump_templates),
-                  "tredgpu_sw_classify")
+        # (a call whose reads are all routed asks nothing of the library's kernels: their packed-value scoring bound,
+        # check_sw_range, would refuse scorings the long kernel takes, such as gap_extend 16)
+        if len(routed) < n_reads:
+            self._chk(self.lib.tredgpu_sw_classify(self.h, MEM_HOST, _ptr(packed), _ptr(read_off), _ptr(masked), n_reads,
+                                                   _ptr(unit_read_off), _ptr(unit_ladder), n_units, C.byref(p), _ptr(out_tag),
+                                                   _ptr(out_h), _ptr(out_score), _ptr(out_dump), dump_templates),
+                      "tredgpu_sw_classify")
         woff = np.asarray(read_off)
         pk = np.asarray(packed)
         sub_off = np.zeros(len(routed) + 1, np.int64)
