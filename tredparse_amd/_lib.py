@@ -63,6 +63,11 @@ CIGAR_EXPORTS = ("tredcigar_sw_cigar", "tredcigar_get_timing", "tredcigar_reset_
                  "tredcigar_last_error")
 CIGAR_OK, CIGAR_NO_PATH, CIGAR_OFF_EDGE, CIGAR_OVERFLOW, CIGAR_TOO_LONG, CIGAR_BAD_ITEM = 0, 1, 2, 3, 4, 5
 
+# the second-best alignment's symbols (include/tredsecond.h)
+SECOND_EXPORTS = ("tredsecond_sw_second", "tredsecond_get_timing", "tredsecond_reset_timing", "tredsecond_release",
+                  "tredsecond_last_error")
+SECOND_OK, SECOND_TOO_LONG, SECOND_BAD_ITEM = 0, 4, 5
+
 # every symbol include/tredgpu.h declares (tests check the .so exports them all)
 EXPORTS = ("tredgpu_create", "tredgpu_destroy", "tredgpu_last_error", "tredgpu_sync", "tredgpu_get_stream",
            "tredgpu_version", "tredgpu_set_ladders", "tredgpu_set_model", "tredgpu_pack_reads",
@@ -111,6 +116,14 @@ def load():
     lib.tredcigar_release.restype = None
     lib.tredcigar_last_error.argtypes = []
     lib.tredcigar_last_error.restype = C.c_char_p
+    lib.tredsecond_sw_second.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                         vp, vp, vp, vp, i64, vp, vp, vp, C.POINTER(SwParams), vp, vp]
+    lib.tredsecond_get_timing.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
+    lib.tredsecond_reset_timing.argtypes = [vp]
+    lib.tredsecond_release.argtypes = [vp]
+    lib.tredsecond_release.restype = None
+    lib.tredsecond_last_error.argtypes = []
+    lib.tredsecond_last_error.restype = C.c_char_p
     lib.tredgpu_get_stream.argtypes = [vp]
     lib.tredgpu_get_stream.restype = vp
     lib.tredgpu_version.restype = C.c_char_p
@@ -252,6 +265,7 @@ class Context:
     def close(self):
         if getattr(self, "h", None):
             self.lib.tredcigar_release(self.h)
+            self.lib.tredsecond_release(self.h)
             self.lib.tredlong_release(self.h)
             self.lib.tredgpu_destroy(self.h)
             self.h = None
@@ -581,11 +595,25 @@ class Context:
             np.asarray(out_n_ops)[sel] = no
             np.asarray(out_status)[sel] = st
 
+    def sw_secondary(self, packed, read_off, read_len, n_items, item_ladder, item_template, mask_len, params, out, out_status,
+                     ladders=None):
+        """tredsecond_sw_second (include/tredsecond.h): what ssw_align reports as score1 / ref_end1 / score2 / ref_end2 for
+        n_items pairs, host memory.  Item k is read k (packed / read_off / read_len as pack_reads writes them) against
+        template item_template[k] (db order) of ladder item_ladder[k] with maskLen mask_len[k] (int32 [n]).  out: int32
+        [n][4], out_status: int32 [n] (SECOND_*).  ladders: the table the indices refer to (default: the one registered
+        with set_ladders).  One unit takes short and long items alike, whether or not the long-read path is on."""
+        table = _ladder_args(list(self.ladders if ladders is None else ladders))
+        rc = self.lib.tredsecond_sw_second(self.h, *table, _ptr(packed), _ptr(read_off), _ptr(read_len), n_items,
+                                           _ptr(item_ladder), _ptr(item_template), _ptr(mask_len), C.byref(params), _ptr(out),
+                                           _ptr(out_status))
+        self._chk_side(rc, "tredsecond_sw_second failed ({})".format(rc), self.lib.tredsecond_last_error)
+
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")
         self._chk_side(self.lib.tredlong_cigar_reset_timing(self.h), "tredlong_cigar_reset_timing failed",
                        self.lib.tredlong_last_error)
         self._chk_side(self.lib.tredcigar_reset_timing(self.h), "tredcigar_reset_timing failed", self.lib.tredcigar_last_error)
+        self._chk_side(self.lib.tredsecond_reset_timing(self.h), "tredsecond_reset_timing failed", self.lib.tredsecond_last_error)
 
     def get_timing(self, which):
         """(launches, total device ms) of kernel `which` since reset_timing (HIP events)."""
@@ -597,6 +625,10 @@ class Context:
         if which == KERNEL_CIGAR_LONG:
             self._chk_side(self.lib.tredlong_cigar_timing(self.h, C.byref(n), C.byref(ms)), "tredlong_cigar_timing failed",
                            self.lib.tredlong_last_error)
+            return n.value, ms.value
+        if which == KERNEL_SECOND:
+            self._chk_side(self.lib.tredsecond_get_timing(self.h, C.byref(n), C.byref(ms)), "tredsecond_get_timing failed",
+                           self.lib.tredsecond_last_error)
             return n.value, ms.value
         self._chk(self.lib.tredgpu_get_timing(self.h, which, C.byref(n), C.byref(ms)), "tredgpu_get_timing")
         return n.value, ms.value
@@ -617,6 +649,7 @@ KERNEL_SW, KERNEL_TALLY, KERNEL_GRID = 0, 1, 2
 KERNEL_GRID_PREPARE, KERNEL_GRID_PAIRS, KERNEL_GRID_REDUCE, KERNEL_GRID_KDE = 3, 4, 5, 6
 KERNEL_CIGAR = 16               # include/tredcigar.h; tredgpu_get_timing's own series ends at 6
 KERNEL_CIGAR_LONG = 17          # tredlong_cigar_timing (include/tredlong.h): a selector of the binding's only
+KERNEL_SECOND = 18              # tredsecond_get_timing (include/tredsecond.h): calls of sw_secondary and their device time
 
 
 def default_sw_params(clip=False, max_read_len=0):

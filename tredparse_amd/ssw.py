@@ -6,6 +6,13 @@ whole template ladders (bam_parser / engine) and never comes through here.  All 
 private GPU context (created on first use, never the engine's: registering a one-template ladder replaces a
 context's ladder table), the reference is re-registered only when it differs from the one registered last, and
 `align_many` takes any number of reads per call.
+
+The reference computes two things on every call that are opt-in here, one kernel launch each per `align_many` and only
+for the queries that pass the min_score / min_len filter: `report_cigar=True` fills the CIGAR (include/tredcigar.h) and
+`report_secondary=True` fills `score2` / `ref_end2` (include/tredsecond.h) -- the best score that ends at least
+len(query) // 2 columns (15 for queries of up to 30 letters) away from the optimal end, as ssw_align's struct has it; the
+reference's own wrapper leaves `score2 = None` whatever the flag says (ssw_wrap.py:304).  On a tandem repeat
+`score - score2` says how firmly the read is placed.
 """
 import numpy as np
 
@@ -22,7 +29,8 @@ def _context():
 
 def set_long_reads(enabled):
     """Switch the long-read path (Context.set_long_reads) of the shared private context: on, Aligners without a context of
-    their own take references of up to 4 095 letters and queries of up to 2 048 bp, report_cigar included."""
+    their own take references of up to 4 095 letters and queries of up to 2 048 bp, report_cigar and report_secondary
+    included."""
     ctx = _context()
     if not enabled and ctx.long_reads:
         ctx.set_ladders([("N", "A", "", 0)])       # (a registered long reference would refuse the switch)
@@ -31,13 +39,13 @@ def set_long_reads(enabled):
 
 
 class PyAlignRes(object):
-    """The reference's result object (ssw_wrap.py:259-383): the five fields, score2 = None, and -- from the operations
-    `ops` (length << 4 | op, M=0 I=1 D=2; empty without report_cigar) -- its cigar_string / cigar, iter_cigar, alignment
-    and str() texts."""
+    """The reference's result object (ssw_wrap.py:259-383): the five fields, score2 / ref_end2 (`second`; None without
+    report_secondary), and -- from the operations `ops` (length << 4 | op, M=0 I=1 D=2; empty without report_cigar) -- its
+    cigar_string / cigar, iter_cigar, alignment and str() texts."""
 
-    def __init__(self, rec, query_seq, ref_seq, ops=()):
+    def __init__(self, rec, query_seq, ref_seq, ops=(), second=None):
         self.score, self.ref_begin, self.ref_end, self.query_begin, self.query_end = (int(x) for x in rec[:5])
-        self.score2 = None
+        self.score2, self.ref_end2 = (None, None) if second is None else (int(second[0]), int(second[1]))
         self.ref_seq, self.query_seq = ref_seq, query_seq
         self._cigar_string = [int(v) for v in ops]
 
@@ -50,6 +58,10 @@ class PyAlignRes(object):
         msg += "Query end        {}\n".format(self.query_end)
         if self.cigar_string:
             msg += "Cigar_string     {}\n".format(self.cigar_string)
+        if self.score2:
+            msg += "SUB-OPTIMAL MATCH\n"
+            msg += "Score 2           {}\n".format(self.score2)
+            msg += "Ref_end2          {}\n".format(self.ref_end2)
         return msg
 
     @property
@@ -99,6 +111,7 @@ class Aligner(object):
         self.ref_seq = ref_seq
         self.match, self.mismatch, self.gap_open, self.gap_extend = match, mismatch, gap_open, gap_extend
         self.report_cigar = bool(report_cigar)   # the reference computes the CIGAR on every call; here it is opt-in
+        self.report_secondary = bool(report_secondary)   # score2 / ref_end2: opt-in as well
         self._own = ctx            # a caller-supplied context is used as is (and its ladders replaced)
 
     def _ready(self):
@@ -128,7 +141,28 @@ class Aligner(object):
         ops = [()] * n
         if self.report_cigar and any(keep):
             ops = self._cigars(ctx, queries, recs, [k for k in range(n) if keep[k]], p, ops)
-        return [PyAlignRes(rec, q, self.ref_seq, o) if k else None for q, rec, k, o in zip(queries, recs, keep, ops)]
+        second = [None] * n
+        if self.report_secondary and any(keep):
+            second = self._seconds(ctx, queries, recs, [k for k in range(n) if keep[k]], p, second)
+        return [PyAlignRes(rec, q, self.ref_seq, o, s2) if k else None
+                for q, rec, k, o, s2 in zip(queries, recs, keep, ops, second)]
+
+    def _seconds(self, ctx, queries, recs, kept, p, second):
+        """ONE sw_secondary call for the queries that passed the filter, maskLen as Aligner.align sets it (ssw_wrap.py:198-201)."""
+        sub = [queries[k] for k in kept]
+        m = len(sub)
+        packed, woff, rlen = _lib.pack_reads(sub)
+        zero = np.zeros(m, np.int32)
+        mask = np.array([len(q) // 2 if len(q) > 30 else 15 for q in sub], np.int32)
+        out, status = np.zeros((m, 4), np.int32), np.zeros(m, np.int32)
+        ctx.sw_secondary(packed, woff, rlen, m, zero, zero, mask, p, out, status, ladders=[(self.ref_seq, "A", "", 0)])
+        second = list(second)
+        for i, k in enumerate(kept):
+            if status[i] != _lib.SECOND_OK or (int(out[i, 0]), int(out[i, 1])) != (int(recs[k][0]), int(recs[k][2])):
+                raise _lib.TredGpuError("sw_secondary: status {} for query {}, score1 / ref_end1 {} / {} against the SW "
+                                        "kernel's {} / {}".format(int(status[i]), k, out[i, 0], out[i, 1], recs[k][0], recs[k][2]))
+            second[k] = out[i, 2:]
+        return second
 
     def _cigars(self, ctx, queries, recs, kept, p, ops):
         """ONE sw_cigar call for the queries that passed the filter; a CIGAR longer than the room gets a second call."""
