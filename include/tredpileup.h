@@ -1,0 +1,79 @@
+/* tredpileup.h -- per-allele evidence from per-read alignments, on the GPU (libtredgpu.so, gfx950), under a prefix of
+ * its own as tredlong.h, tredcigar.h and tredsecond.h are (tredgpu.h is the ABI of the kernels the profiles under
+ * profiles/ were taken from).
+ *
+ * tredcigar_sw_cigar says how ONE read lies on the template it was counted for.  tredpileup_pileup adds the reads of a
+ * group -- the reads counted for one allele of one locus -- up, column by column of that allele's FORWARD template: which
+ * letter each read shows there, whether it skips the column, and what it inserts before it.  That table is what a
+ * consensus of the tract, and so an interruption of it (CAA in HTT, AGG in FMR1), is read from.
+ *
+ * Opt-in: nothing else in libtredgpu calls it (Engine.consensus, tred.py --consensus).
+ */
+#ifndef TREDPILEUP_H
+#define TREDPILEUP_H
+
+#include "tredgpu.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define TREDGPU_PILEUP_OK 0
+#define TREDGPU_PILEUP_TOO_LONG 4  /* read beyond TREDGPU_MAX_LONG_READ_LEN or template beyond TREDGPU_MAX_LONG_TEMPLATE_LEN
+                                      (tredlong.h); the values are those of TREDGPU_CIGAR_TOO_LONG / _BAD_ITEM */
+#define TREDGPU_PILEUP_BAD_ITEM 5  /* ladder, template or group index out of range; fields outside the pair; n_ops < 1 or
+                                      > cap; an operation other than M / I / D or of length 0; M + D lengths that are not
+                                      ref_end - ref_begin + 1 or M + I lengths that are not read_end - read_begin + 1; a
+                                      (ladder, units) other than that of the group's first accepted item */
+
+#define TREDGPU_PILEUP_CHANNELS 8
+#define TREDGPU_PILEUP_MAX_STRIDE 65536
+#define TREDGPU_KERNEL_PILEUP 19   /* the timing selector of the binding (tredsecond.h has 18) */
+
+/*
+ * The pileup of n_items alignments in n_groups groups on the context's stream.  HOST memory only: copies in, runs, copies
+ * out, waits.
+ *   n_ladders, prefix, repeat, suffix, max_units, packed, read_off, read_len, item_ladder, item_template, fields
+ *                      the items, exactly as tredcigar_sw_cigar takes them (item_template in db order: u=1 fwd, u=1 rc,
+ *                      u=2 fwd, ...; 0 for a plain reference); the scoring is not needed
+ *   ops                uint32 [n_items][cap] and n_ops[n_items]: that call's out_ops / out_n_ops (length << 4 | op, M=0 I=1
+ *                      D=2, oldest first)
+ *   item_group[n_items], n_groups   the group of every item.  All items of a group name the same ladder and the same
+ *                      units (item_template / 2), strands mixed freely; the group takes its shape from its first accepted
+ *                      item, in the caller's order
+ *   stride             columns of a group's table: at least the largest template length of the ladders (as far as an item
+ *                      can be accepted: TREDGPU_MAX_LONG_TEMPLATE_LEN at the most) + 1, at most TREDGPU_PILEUP_MAX_STRIDE
+ *   out_counts         int32 [n_groups][stride][8], written whole (a group without an accepted item is all zeros).  Column
+ *                      c is column c of the FORWARD template of the group's (ladder, units), whichever strand an item lies
+ *                      on.  Channels 0-3: reads showing A, C, G, T at the column under an M operation; 4: N; 5: reads
+ *                      whose D operation covers the column; 6: insertions that sit immediately before the column (events);
+ *                      7: their summed length.  Slot L (the template's length) takes an insertion behind the last column.
+ *                      An item on a reverse-complement template of length L (odd item_template, max_units > 0) counts
+ *                      its column c at L - 1 - c, its letter complemented (N stays N), and an insertion before c before
+ *                      L - c.  Soft-clipped read ends count nowhere.
+ *   out_status[n_items] (TREDGPU_PILEUP_*).  An item is validated completely before it counts anything, a refused item
+ *                      counts nothing, and no index derived from an item is used before it is checked.
+ * Every cell of out_counts is owned by one workgroup, which adds in LDS and stores once: the result is exact and does not
+ * depend on the order of the items (csrc/pileup.hip).
+ * Returns 0, -2 bad arguments (stride too small included: nothing is written then), -10 HIP error;
+ * tredpileup_last_error() has the text (per thread).  tredpileup_release frees what the calls on a context hold (ladder
+ * table, staging buffers, timing events): call it before tredgpu_destroy; calling it again, or before any call, does
+ * nothing.
+ */
+int tredpileup_pileup(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat,
+                      const char* const* suffix, const int32_t* max_units, const uint32_t* packed, const int64_t* read_off,
+                      const int32_t* read_len, int64_t n_items, const int32_t* item_ladder, const int32_t* item_template,
+                      const int16_t* fields, const uint32_t* ops, int32_t cap, const int32_t* n_ops, const int32_t* item_group,
+                      int32_t n_groups, int32_t stride, int32_t* out_counts, int32_t* out_status);
+/* calls of tredpileup_pileup on this context since tredpileup_reset_timing and the summed device time of their kernels
+   (HIP events, one pair around the launches of a call) */
+int tredpileup_get_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms);
+int tredpileup_reset_timing(tredgpu_ctx* ctx);
+void tredpileup_release(tredgpu_ctx* ctx);
+const char* tredpileup_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -68,6 +68,12 @@ SECOND_EXPORTS = ("tredsecond_sw_second", "tredsecond_get_timing", "tredsecond_r
                   "tredsecond_last_error")
 SECOND_OK, SECOND_TOO_LONG, SECOND_BAD_ITEM = 0, 4, 5
 
+# the pileup's symbols (include/tredpileup.h)
+PILEUP_EXPORTS = ("tredpileup_pileup", "tredpileup_get_timing", "tredpileup_reset_timing", "tredpileup_release",
+                  "tredpileup_last_error")
+PILEUP_OK, PILEUP_TOO_LONG, PILEUP_BAD_ITEM = 0, 4, 5
+PILEUP_CHANNELS = 8             # A C G T N, deleted, insertions before the column, their summed length
+
 # every symbol include/tredgpu.h declares (tests check the .so exports them all)
 EXPORTS = ("tredgpu_create", "tredgpu_destroy", "tredgpu_last_error", "tredgpu_sync", "tredgpu_get_stream",
            "tredgpu_version", "tredgpu_set_ladders", "tredgpu_set_model", "tredgpu_pack_reads",
@@ -124,6 +130,14 @@ def load():
     lib.tredsecond_release.restype = None
     lib.tredsecond_last_error.argtypes = []
     lib.tredsecond_last_error.restype = C.c_char_p
+    lib.tredpileup_pileup.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                      vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp]
+    lib.tredpileup_get_timing.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
+    lib.tredpileup_reset_timing.argtypes = [vp]
+    lib.tredpileup_release.argtypes = [vp]
+    lib.tredpileup_release.restype = None
+    lib.tredpileup_last_error.argtypes = []
+    lib.tredpileup_last_error.restype = C.c_char_p
     lib.tredgpu_get_stream.argtypes = [vp]
     lib.tredgpu_get_stream.restype = vp
     lib.tredgpu_version.restype = C.c_char_p
@@ -266,6 +280,7 @@ class Context:
         if getattr(self, "h", None):
             self.lib.tredcigar_release(self.h)
             self.lib.tredsecond_release(self.h)
+            self.lib.tredpileup_release(self.h)
             self.lib.tredlong_release(self.h)
             self.lib.tredgpu_destroy(self.h)
             self.h = None
@@ -608,12 +623,28 @@ class Context:
                                            _ptr(out_status))
         self._chk_side(rc, "tredsecond_sw_second failed ({})".format(rc), self.lib.tredsecond_last_error)
 
+    def pileup(self, packed, read_off, read_len, n_items, item_ladder, item_template, fields, ops, cap, n_ops, item_group,
+               n_groups, stride, out_counts, out_status, ladders=None):
+        """tredpileup_pileup (include/tredpileup.h): the items of sw_cigar -- packed / read_off / read_len, item_ladder,
+        item_template, fields as given to it, ops (uint32 [n][cap]) and n_ops as it returned them -- counted per group
+        (item_group int32 [n], 0 .. n_groups - 1) and per column of the group's forward template, host memory.  out_counts:
+        int32 [n_groups][stride][PILEUP_CHANNELS] (A C G T N under an M operation, deleted, insertions before the column
+        and their summed length), stride at least the longest template + 1; out_status: int32 [n] (PILEUP_*).  ladders: the
+        table the indices refer to (default: the one registered with set_ladders).  One unit takes short and long items
+        alike, whether or not the long-read path is on."""
+        table = _ladder_args(list(self.ladders if ladders is None else ladders))
+        rc = self.lib.tredpileup_pileup(self.h, *table, _ptr(packed), _ptr(read_off), _ptr(read_len), n_items,
+                                        _ptr(item_ladder), _ptr(item_template), _ptr(fields), _ptr(ops), cap, _ptr(n_ops),
+                                        _ptr(item_group), n_groups, stride, _ptr(out_counts), _ptr(out_status))
+        self._chk_side(rc, "tredpileup_pileup failed ({})".format(rc), self.lib.tredpileup_last_error)
+
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")
         self._chk_side(self.lib.tredlong_cigar_reset_timing(self.h), "tredlong_cigar_reset_timing failed",
                        self.lib.tredlong_last_error)
         self._chk_side(self.lib.tredcigar_reset_timing(self.h), "tredcigar_reset_timing failed", self.lib.tredcigar_last_error)
         self._chk_side(self.lib.tredsecond_reset_timing(self.h), "tredsecond_reset_timing failed", self.lib.tredsecond_last_error)
+        self._chk_side(self.lib.tredpileup_reset_timing(self.h), "tredpileup_reset_timing failed", self.lib.tredpileup_last_error)
 
     def get_timing(self, which):
         """(launches, total device ms) of kernel `which` since reset_timing (HIP events)."""
@@ -629,6 +660,10 @@ class Context:
         if which == KERNEL_SECOND:
             self._chk_side(self.lib.tredsecond_get_timing(self.h, C.byref(n), C.byref(ms)), "tredsecond_get_timing failed",
                            self.lib.tredsecond_last_error)
+            return n.value, ms.value
+        if which == KERNEL_PILEUP:
+            self._chk_side(self.lib.tredpileup_get_timing(self.h, C.byref(n), C.byref(ms)), "tredpileup_get_timing failed",
+                           self.lib.tredpileup_last_error)
             return n.value, ms.value
         self._chk(self.lib.tredgpu_get_timing(self.h, which, C.byref(n), C.byref(ms)), "tredgpu_get_timing")
         return n.value, ms.value
@@ -650,6 +685,7 @@ KERNEL_GRID_PREPARE, KERNEL_GRID_PAIRS, KERNEL_GRID_REDUCE, KERNEL_GRID_KDE = 3,
 KERNEL_CIGAR = 16               # include/tredcigar.h; tredgpu_get_timing's own series ends at 6
 KERNEL_CIGAR_LONG = 17          # tredlong_cigar_timing (include/tredlong.h): a selector of the binding's only
 KERNEL_SECOND = 18              # tredsecond_get_timing (include/tredsecond.h): calls of sw_secondary and their device time
+KERNEL_PILEUP = 19              # tredpileup_get_timing (include/tredpileup.h): calls of pileup and their device time
 
 
 def default_sw_params(clip=False, max_read_len=0):

@@ -1,0 +1,279 @@
+// pileup.hip -- per-allele evidence from per-read alignments (tredpileup_pileup, include/tredpileup.h): the items of a
+// group -- (read, template, fields, CIGAR operations) as tredcigar_sw_cigar takes and returns them -- counted column by
+// column of the group's forward template into int32 [n_groups][stride][8].  A unit of its own, outside the source hash
+// the profiles are tied to (csrc/Makefile); the host harness is cigar_unit.h's and ladder_host.h's.
+//
+// Two kernels per call.
+//   * validate_kernel, one lane per item: every refusal of the header that an item can be given on its own (indices,
+//     lengths, fields, the operations and their sums) -> pre[item] and out_status[item].  Nothing an item names is used
+//     as an index before the check that bounds it, and the counting kernel only ever looks at items with pre == OK.
+//   * pileup_kernel, one WORKGROUP of four wavefronts per (group, 512-column tile), the work units taken grid-stride by
+//     at most MAX_BLOCKS workgroups.  The host has sorted the items by group (order / goff: a CSR in the caller's order),
+//     so a workgroup reads its group's list and nobody else's.  It zeroes 8 x 512 int32 counters in LDS (16 KB), finds
+//     the group's first accepted item (an LDS atomicMin over the list) and with it the group's (ladder, units) and
+//     length; then its wavefronts take the group's items in turn.  A wavefront walks the
+//     item's operations -- the walk is uniform over the wave -- and its lanes spread over the columns of ONE operation,
+//     intersected with the tile: they hit 64 different columns, and with the counters laid out [channel][column] 64
+//     different LDS banks whatever the letters are.  Adds are ds_add_u32 (atomicAdd on LDS, result unused): two wavefronts
+//     may be on the same column.  At the end the tile is stored once, with plain vector stores, coalesced, zeros included
+//     -- every cell of out_counts has exactly one owner, there is no global atomic, and the result is exact and order-free.
+//     The workgroup of a group's tile 0 also refuses the accepted items whose (ladder, units) is not the group's.
+//   * counters are 32-bit: a group may hold any number of items a call can carry (n_items < 2^31).
+#include <climits>
+#include <cstring>
+
+#include "cigar_unit.h"
+#include "../../include/tredlong.h"
+#include "../../include/tredpileup.h"
+
+namespace {
+using namespace cigar_unit;
+
+thread_local std::string g_pileup_error;   // the text of tredpileup_last_error()
+
+constexpr int TILE = 512;                  // columns of a work unit
+constexpr int CH = TREDGPU_PILEUP_CHANNELS;
+constexpr int THREADS = 256, WAVES = THREADS / 64;
+// workgroups of a launch at the most.  256 CUs hold 2 048 at once (8 each by registers: 48 VGPRs, 8 waves per SIMD; by
+// LDS, 16 388 B, it would be 9), but a workgroup that takes a second unit is the launch's tail: 4 567 units took 0.061 ms
+// on 2 048 workgroups, 0.056 ms on 2 560 and 0.054 ms on 4 096 (DESIGN, "Per-allele pileup and consensus")
+constexpr int MAX_BLOCKS = 4096;
+
+struct PileArgs {
+    const uint32_t* packed;
+    const int64_t* read_off;
+    const int32_t *read_len, *item_ladder, *item_template;
+    const int16_t* fields;
+    const uint32_t* ops;
+    const int32_t *n_ops, *item_group;
+    const LadderRecord* ladders;
+    int32_t n_ladders, cap, n_groups, stride, ntile;
+    int64_t n_items;
+    const int32_t* order;      // the items with a group in range, sorted by group, the caller's order within a group
+    const int64_t* goff;       // [n_groups + 1] into order
+    int32_t* pre;              // [n_items]: the status of validate_kernel
+    int32_t* out_counts;       // [n_groups][stride][CH]
+    int32_t* out_status;
+};
+
+// the length of template tpl (in range) of a ladder; both strands have the same
+__device__ __forceinline__ int template_len(const LadderRecord& d, int tpl) {
+    return d.alen[0] + (d.max_units > 0 ? d.period * (tpl / 2 + 1) : 0) + d.blen[0];
+}
+
+__device__ int validate(const PileArgs& a, int64_t item) {
+    const int g = a.item_group[item];
+    if (g < 0 || g >= a.n_groups) return TREDGPU_PILEUP_BAD_ITEM;
+    const int lad = a.item_ladder[item], tpl = a.item_template[item];
+    if (lad < 0 || lad >= a.n_ladders) return TREDGPU_PILEUP_BAD_ITEM;
+    const LadderRecord d = a.ladders[lad];
+    if (tpl < 0 || tpl >= (d.max_units > 0 ? 2 * d.max_units : 1)) return TREDGPU_PILEUP_BAD_ITEM;
+    const int tlen = template_len(d, tpl), L = a.read_len[item];
+    if (L > TREDGPU_MAX_LONG_READ_LEN || tlen > TREDGPU_MAX_LONG_TEMPLATE_LEN) return TREDGPU_PILEUP_TOO_LONG;
+    const int16_t* fl = a.fields + (size_t)item * 5;
+    const int ref_begin = fl[1], ref_end = fl[2], read_begin = fl[3], read_end = fl[4];
+    if (ref_begin < 0 || ref_end < ref_begin || ref_end >= tlen || read_begin < 0 || read_end < read_begin || read_end >= L)
+        return TREDGPU_PILEUP_BAD_ITEM;
+    const int n = a.n_ops[item];
+    if (n < 1 || n > a.cap) return TREDGPU_PILEUP_BAD_ITEM;
+    const uint32_t* ops = a.ops + (size_t)item * a.cap;
+    int64_t on_ref = 0, on_read = 0;
+    for (int j = 0; j < n; ++j) {
+        const uint32_t op = ops[j] & 15u, len = ops[j] >> 4;
+        if (op > 2u || len == 0u) return TREDGPU_PILEUP_BAD_ITEM;
+        if (op != 1u) on_ref += len;
+        if (op != 2u) on_read += len;
+    }
+    if (on_ref != ref_end - ref_begin + 1 || on_read != read_end - read_begin + 1) return TREDGPU_PILEUP_BAD_ITEM;
+    return TREDGPU_PILEUP_OK;
+}
+
+__global__ __launch_bounds__(256) void validate_kernel(PileArgs a) {
+    const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= a.n_items) return;
+    const int status = validate(a, item);
+    a.pre[item] = status;
+    a.out_status[item] = status;
+}
+
+// One accepted item of the group into the tile [tile0, tile0 + TILE) of cnt ([CH][TILE]); T: the template's length.
+// The whole wavefront is here with the same item.
+__device__ __forceinline__ void count_item(const PileArgs& a, int64_t item, int strand, int T, int tile0, int* cnt) {
+    const int lane = threadIdx.x & 63;
+    const int16_t* fl = a.fields + (size_t)item * 5;
+    const int ref_begin = fl[1], ref_end = fl[2];
+    // the forward columns and slots the item can touch: its columns and the slot behind the last
+    const int lo = strand ? T - 1 - ref_end : ref_begin, hi = strand ? T - ref_begin : ref_end + 1;
+    if (hi < tile0 || lo >= tile0 + TILE) return;
+    const uint32_t* rec = a.packed + a.read_off[item];
+    const int nb = (a.read_len[item] + 15) >> 4;
+    const uint32_t* ops = a.ops + (size_t)item * a.cap;
+    const int n = a.n_ops[item];
+    int r = ref_begin, q = fl[3];
+    for (int j = 0; j < n; ++j) {
+        const int op = (int)(ops[j] & 15u), len = (int)(ops[j] >> 4);
+        if (op == 1) {                                             // an insertion before column r of the item's strand
+            const int slot = (strand ? T - r : r) - tile0;
+            if (lane == 0 && slot >= 0 && slot < TILE) {
+                atomicAdd(&cnt[6 * TILE + slot], 1);
+                atomicAdd(&cnt[7 * TILE + slot], len);
+            }
+            q += len;
+            continue;
+        }
+        // k in [klo, khi): the steps of the operation whose forward column r + k, or T - 1 - r - k, lies in the tile
+        const int base = strand ? T - 1 - r : r;
+        const int klo = strand ? max(0, base - tile0 - TILE + 1) : max(0, tile0 - base);
+        const int khi = strand ? min(len, base - tile0 + 1) : min(len, tile0 + TILE - base);
+        for (int k = klo + lane; k < khi; k += 64) {
+            const int col = (strand ? base - k : base + k) - tile0;
+            int ch = 5;
+            if (op == 0) {
+                const int code = read_code(rec, nb, q + k);
+                ch = (strand && code < 4) ? 3 - code : code;
+            }
+            atomicAdd(&cnt[ch * TILE + col], 1);
+        }
+        r += len;
+        if (op == 0) q += len;
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void pileup_kernel(PileArgs a) {
+    __shared__ int cnt[CH * TILE];
+    __shared__ int first;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t n_work = (int64_t)a.n_groups * a.ntile;
+    for (int64_t w = blockIdx.x; w < n_work; w += gridDim.x) {
+        const int g = (int)(w / a.ntile), tile0 = (int)(w % a.ntile) * TILE;
+        const int64_t lo = a.goff[g], hi = a.goff[g + 1];
+        __syncthreads();                                           // the unit before has stored its tile
+        for (int k = threadIdx.x; k < CH * TILE; k += THREADS) cnt[k] = 0;
+        if (threadIdx.x == 0) first = INT_MAX;
+        __syncthreads();
+        for (int64_t k = lo + threadIdx.x; k < hi; k += THREADS)
+            if (a.pre[a.order[k]] == TREDGPU_PILEUP_OK) { atomicMin(&first, (int)(k - lo)); break; }
+        __syncthreads();
+        const int f = first;
+        if (f != INT_MAX) {
+            const int it0 = a.order[lo + f];                       // accepted: its ladder and template are in range
+            const int lad0 = a.item_ladder[it0], units0 = a.item_template[it0] >> 1;
+            const LadderRecord d = a.ladders[lad0];
+            const int T = template_len(d, 2 * units0);
+            for (int64_t k = lo + wave; k < hi; k += WAVES) {
+                const int item = a.order[k];
+                if (a.pre[item] != TREDGPU_PILEUP_OK) continue;
+                const int tpl = a.item_template[item];
+                if (a.item_ladder[item] != lad0 || (tpl >> 1) != units0) {
+                    if (tile0 == 0 && lane == 0) a.out_status[item] = TREDGPU_PILEUP_BAD_ITEM;
+                    continue;
+                }
+                if (tile0 <= T) count_item(a, item, d.max_units > 0 ? (tpl & 1) : 0, T, tile0, cnt);
+            }
+        }
+        __syncthreads();
+        int32_t* out = a.out_counts + ((size_t)g * a.stride + tile0) * CH;
+        const int cols = min(TILE, a.stride - tile0);
+        for (int k = threadIdx.x; k < cols * CH; k += THREADS) out[k] = cnt[(k % CH) * TILE + k / CH];
+    }
+}
+
+// st: the six item inputs, ops, n_ops and out_status; the rest is the unit's
+struct State : StateBase { Dev group, order, goff, pre, counts; };
+Registry<State> g_states;
+
+}  // namespace
+
+extern "C" {
+
+int tredpileup_pileup(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat,
+                      const char* const* suffix, const int32_t* max_units, const uint32_t* packed, const int64_t* read_off,
+                      const int32_t* read_len, int64_t n_items, const int32_t* item_ladder, const int32_t* item_template,
+                      const int16_t* fields, const uint32_t* ops, int32_t cap, const int32_t* n_ops, const int32_t* item_group,
+                      int32_t n_groups, int32_t stride, int32_t* out_counts, int32_t* out_status) {
+    std::string& err = g_pileup_error;
+    err.clear();
+    const Table t{n_ladders, prefix, repeat, suffix, max_units};
+    const tredgpu_sw_params any_scoring = {1, 5, 7, 2, 0, 0, 0, 0};     // (the scoring is not needed; the shared check wants one)
+    int rc = call_refusal(err, ctx, true, t, n_items, cap, &any_scoring,
+                          {packed, read_off, read_len, item_ladder, item_template, fields, ops, n_ops, item_group, out_status});
+    if (rc) return rc;
+    if (n_groups < 0 || (n_groups > 0 && !out_counts)) return fail(err, -2, "n_groups must not be negative, nor out_counts NULL");
+    size_t longest = 0;
+    for (int i = 0; i < n_ladders; ++i) {
+        if (!prefix[i] || !repeat[i] || !suffix[i]) return fail(err, -2, "ladder %d: NULL sequence", i);
+        const size_t T = max_units[i] > 0 ? strlen(prefix[i]) + strlen(suffix[i]) + strlen(repeat[i]) * (size_t)max_units[i]
+                                          : strlen(prefix[i]);
+        longest = std::max(longest, std::min<size_t>(T, TREDGPU_MAX_LONG_TEMPLATE_LEN));
+    }
+    if (stride <= 0 || (size_t)stride < longest + 1 || stride > TREDGPU_PILEUP_MAX_STRIDE)
+        return fail(err, -2, "stride %d must be at least the largest template length + 1 = %zu and at most %d", stride,
+                    longest + 1, TREDGPU_PILEUP_MAX_STRIDE);
+    const size_t n = (size_t)n_items, cells = (size_t)n_groups * stride * CH;
+    if (n_items == 0 || n_groups == 0) {                           // nothing to launch: the table is written whole all the same
+        if (cells) memset(out_counts, 0, cells * 4);
+        for (size_t k = 0; k < n; ++k) out_status[k] = TREDGPU_PILEUP_BAD_ITEM;     // (no group is in range)
+        return 0;
+    }
+    if ((rc = reads_refusal(err, read_off, read_len, n, TREDGPU_MAX_LONG_READ_LEN))) return rc;
+    hipStream_t st;
+    if ((rc = select_device(err, ctx, st))) return rc;
+    State& s = *g_states.state_of(ctx);
+    if ((rc = set_ladders(err, s, st, t, 0))) return rc;           // (a template beyond the limit is the item's TOO_LONG)
+
+    // the items by group, in the caller's order within a group; an item whose group is out of range is in no list
+    std::vector<int64_t> goff((size_t)n_groups + 1, 0);
+    auto in_range = [&](size_t k) { return item_group[k] >= 0 && item_group[k] < n_groups; };
+    for (size_t k = 0; k < n; ++k)
+        if (in_range(k)) goff[(size_t)item_group[k] + 1] += 1;
+    for (int g = 0; g < n_groups; ++g) goff[g + 1] += goff[g];
+    std::vector<int32_t> order((size_t)goff[n_groups] + 1);
+    {
+        std::vector<int64_t> fill(goff.begin(), goff.end() - 1);
+        for (size_t k = 0; k < n; ++k)
+            if (in_range(k)) order[(size_t)fill[item_group[k]]++] = (int32_t)k;
+    }
+
+    const size_t sizes[9] = {(size_t)read_off[n] * 4, (n + 1) * 8, n * 4, n * 4, n * 4, n * 10, n * (size_t)cap * 4, n * 4, n * 4};
+    const void* src[9] = {packed, read_off, read_len, item_ladder, item_template, fields, ops, n_ops, nullptr};
+    for (int k = 0; k < 9; ++k)
+        if ((rc = ensure(err, s.st[k], sizes[k], st))) return rc;
+    Dev* own[5] = {&s.group, &s.order, &s.goff, &s.pre, &s.counts};
+    const size_t own_sizes[5] = {n * 4, order.size() * 4, goff.size() * 8, n * 4, cells * 4};
+    const void* own_src[5] = {item_group, order.data(), goff.data(), nullptr, nullptr};
+    for (int k = 0; k < 5; ++k)
+        if ((rc = ensure(err, *own[k], own_sizes[k], st))) return rc;
+    for (int k = 0; k < 9; ++k)
+        if (src[k] && sizes[k]) CIGAR_UNIT_CHK(err, hipMemcpyAsync(s.st[k].p, src[k], sizes[k], hipMemcpyHostToDevice, st));
+    for (int k = 0; k < 5; ++k)
+        if (own_src[k]) CIGAR_UNIT_CHK(err, hipMemcpyAsync(own[k]->p, own_src[k], own_sizes[k], hipMemcpyHostToDevice, st));
+
+    PileArgs a{};
+    a.packed = (const uint32_t*)s.st[0].p; a.read_off = (const int64_t*)s.st[1].p; a.read_len = (const int32_t*)s.st[2].p;
+    a.item_ladder = (const int32_t*)s.st[3].p; a.item_template = (const int32_t*)s.st[4].p; a.fields = (const int16_t*)s.st[5].p;
+    a.ops = (const uint32_t*)s.st[6].p; a.n_ops = (const int32_t*)s.st[7].p; a.out_status = (int32_t*)s.st[8].p;
+    a.item_group = (const int32_t*)s.group.p; a.order = (const int32_t*)s.order.p; a.goff = (const int64_t*)s.goff.p;
+    a.pre = (int32_t*)s.pre.p; a.out_counts = (int32_t*)s.counts.p;
+    a.ladders = (const LadderRecord*)s.ladders.p; a.n_ladders = s.n_ladders;
+    a.n_items = n_items; a.cap = cap; a.n_groups = n_groups; a.stride = stride; a.ntile = (stride + TILE - 1) / TILE;
+
+    if ((rc = timed_begin(err, s, st))) return rc;
+    hipLaunchKernelGGL(validate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    const int64_t n_work = (int64_t)n_groups * a.ntile;
+    hipLaunchKernelGGL(pileup_kernel, dim3((unsigned)std::min<int64_t>(n_work, MAX_BLOCKS)), dim3(THREADS), 0, st, a);
+    if ((rc = timed_end(err, s, st))) return rc;
+    CIGAR_UNIT_CHK(err, hipMemcpyAsync(out_counts, a.out_counts, cells * 4, hipMemcpyDeviceToHost, st));
+    CIGAR_UNIT_CHK(err, hipMemcpyAsync(out_status, a.out_status, n * 4, hipMemcpyDeviceToHost, st));
+    CIGAR_UNIT_CHK(err, hipStreamSynchronize(st));                 // (order and goff are read by the copies above until here)
+    return 0;
+}
+
+int tredpileup_get_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms) { return timing(g_pileup_error, g_states, ctx, launches, total_ms, false); }
+
+int tredpileup_reset_timing(tredgpu_ctx* ctx) { return timing(g_pileup_error, g_states, ctx, nullptr, nullptr, true); }
+
+void tredpileup_release(tredgpu_ctx* ctx) { release(g_states, ctx, {&State::group, &State::order, &State::goff, &State::pre, &State::counts}); }
+
+const char* tredpileup_last_error(void) { return g_pileup_error.c_str(); }
+
+}  // extern "C"

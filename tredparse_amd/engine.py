@@ -218,7 +218,7 @@ class _SelectedBatch(object):
 class BatchResult(object):
     """Arrays of one genotyped PackedUnits batch; unit(i) gives the per-unit view the callers format."""
     __slots__ = ("batch", "tag", "h", "score", "full", "pref", "rept", "calls", "marg", "joint", "grid", "grid_off",
-                 "joint_units", "repeatpairs", "_emit", "alignments")
+                 "joint_units", "repeatpairs", "_emit", "alignments", "consensus")
 
     def unit(self, i):
         b = self.batch
@@ -240,6 +240,8 @@ class BatchResult(object):
         r.P_h1, r.P_h2 = self.marg[i, 0], self.marg[i, 1]
         al = getattr(self, "alignments", None)
         r.alignments = al[i] if al is not None else None           # Engine.alignments' entry of the unit (--alignments)
+        co = getattr(self, "consensus", None)
+        r.consensus = co[i] if co is not None else None            # Engine.consensus' entry of the unit (--consensus)
         return r
 
 
@@ -247,7 +249,15 @@ class UnitResult(object):
     """grid: the dense dump {h1, h2, ml1..ml4} per pair (only when asked for); joint: (triples {h1, h2, exp(ml - max)}
     of the pairs >= e^-10, total over all distinct pairs) -- what P_h1h2 is printed from."""
     __slots__ = ("tags", "hs", "scores", "full", "pref", "rept_hist", "rept", "call", "grid", "joint", "P_h1", "P_h2",
-                 "joint_units", "alignments")
+                 "joint_units", "alignments", "consensus")
+
+
+class _Winners(object):
+    """Engine.winners' result: per tagged read of the units (m of them, in batch order) tag, h, the read's index in the
+    batch (items), the winning template (win, db order) and its dump row (best), the unit (unit_of), the read's text; and
+    the arguments and outputs of the sw_cigar call over them (item_ladder, fields, ops, n_ops, cap).  uro: the units' read
+    offsets.  Without a tagged read only items (empty) and uro are set."""
+    __slots__ = ("tag", "h", "uro", "items", "win", "best", "unit_of", "reads", "item_ladder", "fields", "ops", "n_ops", "cap")
 
 
 class ReadAlignment(object):
@@ -479,19 +489,18 @@ class Engine(object):
         return tag[:n], h[:n], sc[:n], uro, (dump[:n] if want_dump else None)
 
     # ---- (1b) the alignment behind every tagged read --------------------------------------------------
-    def alignments(self, units):
-        """Per unit: {read index in the unit: ReadAlignment} for every tagged read (HANG included).  classify with the
-        dump, then per tagged read the winning dump row -- the highest score, then the fewest units, then the first row
-        in db order (bam_parser.py:174), which is the pair out_tag / out_h stand for -- and ONE sw_cigar call for all
-        winners."""
-        from .bam_parser import rc
-        from .ssw import PyAlignRes
+    def winners(self, units):
+        """What alignments and consensus share: classify with the dump, then per tagged read (HANG included) the winning
+        dump row -- the highest score, then the fewest units, then the first row in db order (bam_parser.py:174), which is
+        the pair out_tag / out_h stand for -- and ONE sw_cigar call for all winners.  Returns a _Winners: hand it to both
+        when both are wanted, so that these steps run once."""
         tag, h, sc, uro, dump = self.classify(units, want_dump=True)
-        out = [{} for _ in units]
         items = np.nonzero(tag != _lib.TAG_NONE)[0]
         m = len(items)
-        if m == 0:
-            return out
+        w = _Winners()
+        w.items, w.uro = items, uro
+        if m == 0:                            # (no tagged read: nothing was asked of sw_cigar)
+            return w
         # rows in db order are u=1 fwd, u=1 rc, u=2 fwd, ...: the first row with the highest score has the fewest units
         rows = dump[items]
         key = np.where(rows[:, :, 5] > 0, rows[:, :, 0].astype(np.int32), -1)
@@ -505,11 +514,12 @@ class Engine(object):
         reads = [units[g].reads[i - int(uro[g])] for g, i in zip(unit_of.tolist(), items.tolist())]
         packed, woff, rlen = _lib.pack_reads(reads)
         fields = np.ascontiguousarray(best[:, :5], np.int16)
+        item_ladder = np.ascontiguousarray(unit_ladder[unit_of])
         clip = bool(units[0].clip)
         cap = 32
         while True:
             ops, n_ops, status = np.zeros((m, cap), np.uint32), np.zeros(m, np.int32), np.zeros(m, np.int32)
-            self.ctx.sw_cigar(_lib.MEM_HOST, packed, woff, rlen, m, np.ascontiguousarray(unit_ladder[unit_of]), win, fields,
+            self.ctx.sw_cigar(_lib.MEM_HOST, packed, woff, rlen, m, item_ladder, win, fields,
                               _lib.default_sw_params(clip=clip), cap, ops, n_ops, status, ladders=self._ladders)
             if not (status == _lib.CIGAR_OVERFLOW).any():
                 break
@@ -518,15 +528,76 @@ class Engine(object):
             k = int(np.nonzero(status != _lib.CIGAR_OK)[0][0])
             raise _lib.TredGpuError("sw_cigar: status {} for read {} of unit {}".format(int(status[k]), int(items[k] - uro[unit_of[k]]),
                                                                                       int(unit_of[k])))
+        w.tag, w.h, w.win, w.best, w.unit_of, w.reads = tag[items], h[items], win, best, unit_of, reads
+        w.item_ladder, w.fields, w.ops, w.n_ops, w.cap = item_ladder, fields, ops, n_ops, cap
+        return w
+
+    def alignments(self, units, winners=None):
+        """Per unit: {read index in the unit: ReadAlignment} for every tagged read (HANG included): the pair the read was
+        tagged for and its CIGAR (winners: what self.winners(units) returned, when the caller already has it)."""
+        from .bam_parser import rc
+        from .ssw import PyAlignRes
+        w = self.winners(units) if winners is None else winners
+        out = [{} for _ in units]
         targets = {}
-        for j in range(m):
-            g, t = int(unit_of[j]), int(win[j])
+        for j in range(len(w.items)):
+            g, t = int(w.unit_of[j]), int(w.win[j])
             if (g, t) not in targets:
                 x = units[g].tred
                 text = x.prefix + x.repeat * (t // 2 + 1) + x.suffix
                 targets[(g, t)] = rc(text) if t % 2 else text
-            al = PyAlignRes(best[j], reads[j], targets[(g, t)], ops[j, :n_ops[j]])
-            out[g][int(items[j] - uro[g])] = ReadAlignment(int(tag[items[j]]), int(h[items[j]]), t % 2, targets[(g, t)], al)
+            al = PyAlignRes(w.best[j], w.reads[j], targets[(g, t)], w.ops[j, :w.n_ops[j]])
+            out[g][int(w.items[j] - w.uro[g])] = ReadAlignment(int(w.tag[j]), int(w.h[j]), t % 2, targets[(g, t)], al)
+        return out
+
+    # ---- (1c) what is in the tract of an allele ---------------------------------------------------------
+    def consensus(self, units, alleles, winners=None):
+        """Per unit: {a: consensus.AlleleConsensus} for every a >= 1 of alleles[unit] (repeat units): the reads of the
+        unit tagged FULL with h == a, laid on prefix + repeat * a + suffix by the alignments of self.winners (winners:
+        what it returned, when the caller already has it) and counted column by column in ONE pileup call for all units
+        and alleles -- one group per (unit, a).  Only FULL reads count: a partial (PREF / POST) or repeat-only read is
+        tagged with the longest template it fits, not with an allele, so it cannot be placed on an allele's template.
+        An allele no FULL read was counted for -- an expansion longer than the reads, say -- comes back with reads = 0,
+        its template in lower case and empty lists."""
+        from .consensus import AlleleConsensus
+        w = self.winners(units) if winners is None else winners
+        group_of, groups = {}, []
+        for g, want in enumerate(alleles):
+            for a in sorted(set(int(x) for x in want)):
+                if a >= 1:
+                    group_of[(g, a)] = len(groups)
+                    groups.append((g, a))
+        out = [{} for _ in units]
+        if not groups:
+            return out
+        stride = max(self.ctx._template_len(l) for l in self._ladders) + 1
+        counts, n_reads = None, np.zeros(len(groups), np.int64)
+        if len(w.items):
+            gid = np.array([group_of.get((g, a), -1) if t == _lib.TAG_FULL else -1
+                            for g, a, t in zip(w.unit_of.tolist(), w.h.tolist(), w.tag.tolist())], np.int32)
+            sel = np.nonzero(gid >= 0)[0]
+            m = len(sel)
+            if m:
+                packed, woff, rlen = _lib.pack_reads([w.reads[j] for j in sel.tolist()])
+                counts = np.zeros((len(groups), stride, _lib.PILEUP_CHANNELS), np.int32)
+                status = np.zeros(m, np.int32)
+                arr = lambda x, dt: np.ascontiguousarray(x[sel], dt)
+                self.ctx.pileup(packed, woff, rlen, m, arr(w.item_ladder, np.int32), arr(w.win, np.int32), arr(w.fields, np.int16),
+                                arr(w.ops, np.uint32), w.cap, arr(w.n_ops, np.int32), arr(gid, np.int32), len(groups), stride,
+                                counts, status, ladders=self._ladders)
+                if (status != _lib.PILEUP_OK).any():
+                    k = int(np.nonzero(status != _lib.PILEUP_OK)[0][0])
+                    j = int(sel[k])
+                    raise _lib.TredGpuError("pileup: status {} for read {} of unit {}".format(
+                        int(status[k]), int(w.items[j] - w.uro[w.unit_of[j]]), int(w.unit_of[j])))
+                n_reads = np.bincount(gid[sel], minlength=len(groups))
+        for k, (g, a) in enumerate(groups):
+            x = units[g].tred
+            T = x.prefix + x.repeat * a + x.suffix
+            table = np.zeros((len(T) + 1, _lib.PILEUP_CHANNELS), np.int32)
+            if n_reads[k]:
+                table[:] = counts[k, :len(T) + 1]          # (a group with reads has a template of the ladder: it fits the stride)
+            out[g][a] = AlleleConsensus(a, n_reads[k], table, T, len(x.prefix), len(x.repeat))
         return out
 
     # ---- the whole path ------------------------------------------------------------------------------

@@ -86,6 +86,9 @@ def set_argparse():
     p.add_argument("--log", choices=("INFO", "DEBUG"), default="INFO", help="log level")
     p.add_argument("--alignments", action="store_true",
                    help="also write <samplekey>.alignments.txt: how every read of `details` was laid on the allele it was counted for")
+    p.add_argument("--consensus", action="store_true",
+                   help="also write <samplekey>.consensus.json: per called allele the consensus of the reads that span it, its "
+                        "depth, the interruptions of the tract and the insertions")
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     p.add_argument("--toy", action="store_true", help=argparse.SUPPRESS)
     g = p.add_argument_group("Performance options")
@@ -247,8 +250,13 @@ def _genotype(engine, picks, o):
             return
         br = engine.genotype_packed(batch, dense=True) if o["log"] == "DEBUG" else engine.genotype_packed(batch)
         br.repeatpairs = kw["repeatpairs"]
-        if o["alignments"]:
-            br.alignments = engine.alignments(_alignment_units(sub, o["clip"]))
+        if o["alignments"] or o["consensus"]:
+            units = _alignment_units(sub, o["clip"])
+            winners = engine.winners(units)                       # classify with the dump and the CIGAR call: once for both
+            if o["alignments"]:
+                br.alignments = engine.alignments(units, winners=winners)
+            if o["consensus"]:
+                br.consensus = engine.consensus(units, _called_alleles(br), winners=winners)
         i = 0
         for si, _, ks in sub:
             if ks:
@@ -280,6 +288,25 @@ def _alignment_units(sub, clip):
             a, b = s.reads_of(k)
             units.append(Unit(s.loci[k], s.readlen, [s.sequence(i) for i in range(a, b)], s.depth[k], s.ploidy[k], (), (), clip=clip))
     return units
+
+
+def _called_alleles(br):
+    """Per unit of a BatchResult the distinct alleles of its call, in repeat units (none where the grid made no call)."""
+    calls, period = br.calls, br.batch.params["period"]
+    return [sorted({int(c["h1"]) // int(p), int(c["h2"]) // int(p)}) if int(c["status"]) == 0 else [] for c, p in zip(calls, period)]
+
+
+def consensus_text(scan, calls, res):
+    """--consensus: {locus: {"alleles": [AlleleConsensus.to_dict(), ...]}} for every called locus, one entry per distinct
+    called allele of at least one unit, smaller first; sorted keys.  res: {locus index: UnitResult with .consensus}."""
+    out = {}
+    for k, name in enumerate(scan.names):
+        r = res.get(k)
+        if r is None or name + ".details" not in calls:
+            continue
+        alleles = sorted(set(int(a) for a in (calls[name + ".1"], calls[name + ".2"]) if int(a) >= 1))
+        out[name] = {"alleles": [r.consensus[a].to_dict() for a in alleles]}
+    return json.dumps(out, sort_keys=True, indent=1) + "\n"
 
 
 def alignments_text(scan, calls, res, repeatpairs):
@@ -318,7 +345,7 @@ def genotype_scans(engine, task_args, scans):
         o = _options(arg)
         # (a scan whose reads the device selected and still holds -- feeder._device_scan -- goes to the call that packs them there)
         on_device = getattr(pick[1], "device", None) is not None
-        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", o["alignments"], on_device)
+        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", o["alignments"], o["consensus"], on_device)
         groups.setdefault(key, (o, []))[1].append(pick)
     parts = {}
 
@@ -876,7 +903,7 @@ def main(args, quiet=False):
         if args.checkexists and not spawned:
             samples = [s for s in samples if not os.path.exists(s[0] + ".json")]
         tasks = [(key, bam, repo, [only] if only else loci, args.maxinsert, args.fullsearch, args.useclippedreads,
-                  not args.noalts, not args.norepeatpairs, args.log) + ((True,) if args.alignments else ())
+                  not args.noalts, not args.norepeatpairs, args.log) + ((args.alignments, args.consensus) if args.alignments or args.consensus else ())
                  for key, bam, only in samples]
         if not tasks:
             return
