@@ -30,10 +30,12 @@ extern "C" {
  * Classify n_reads reads (HOST memory, tredgpu_pack_reads layout) on the context's stream; read r is aligned against
  * ladder read_ladder[r] of the n_ladders given here (tredgpu_set_ladders' arguments and layout; the context's own
  * table is not used or changed).  out_dump (optional): [n_reads][dump_templates][6] int16 as in tredgpu_sw_classify.
- * Waits for the results.  Cost beyond the kernel: every call allocates and frees its device buffers and copies from
- * the caller's pageable arrays (a few hundred microseconds per call) -- meant for the minority of reads the short
- * kernels cannot hold; a sample whose reads are all longer than TREDGPU_MAX_READ_LEN sends all of them here.  Returns 0, -2 bad arguments, -5 a read beyond TREDGPU_MAX_LONG_READ_LEN, -10 HIP error;
- * the message is in tredlong_last_error() (per thread).
+ * read_off[0] must not be negative (-2, "read_off must be monotone"), and read r has exactly the words of its length.
+ * Waits for the results.  The context keeps the packed ladder table (uploaded again only when a call names another one)
+ * and the staging buffers between calls, grow-only; tredlong_release frees them.  Cost beyond the kernel: the copies
+ * from and to the caller's pageable arrays -- meant for the minority of reads the short kernels cannot hold; a sample
+ * whose reads are all longer than TREDGPU_MAX_READ_LEN sends all of them here.  Returns 0, -2 bad arguments, -5 a read
+ * beyond TREDGPU_MAX_LONG_READ_LEN, -10 HIP error; the message is in tredlong_last_error() (per thread).
  */
 int tredlong_sw_classify(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat,
                              const char* const* suffix, const int32_t* max_units, const uint32_t* packed,
@@ -54,7 +56,8 @@ const char* tredlong_last_error(void);
  * Workspace: a wavefront owns one byte per cell of the call's largest rectangle (ref_end - ref_begin + 1) x (read_end -
  * read_begin + 1) -- 8.4 MB for 2 048 x 4 095 -- and the launch has fewer wavefronts where 256 of them would exceed 1 GiB.
  * The context keeps it between calls, grow-only, with the ladder table and the staging buffers; tredlong_release frees
- * all of it (call it before tredgpu_destroy; calling it again, or before any call, does nothing).
+ * all of it and what tredlong_sw_classify holds (call it before tredgpu_destroy; calling it again, or before any call,
+ * does nothing).
  * Cost: a pass over a band of b columns and r rows is r * ceil(b / 64) steps of one wavefront; the band starts at
  * |refLen - readLen| + 1 and doubles as the reference's does, and the traceback is one lane's walk over at most refLen +
  * readLen cells.  Meant for the minority of reads the short kernels cannot hold.

@@ -3,12 +3,15 @@
 //   L PREFIX REPEAT SUFFIX MAX_UNITS              -> "strands N period P max_units M" and per strand "ALEN BLEN TRUNK BRANCH"
 //                                                    (tab-separated, letters ACGTN), or "refused RC TEXT"
 //   S MATCH MISMATCH GAP_OPEN GAP_EXTEND FLANK 0|1 -> "scoring ok" or "scoring TEXT" (last argument: the flank switch)
-// and of what the two CIGAR units share (a sequence given as NULL is a null pointer):
+// and of what the units' entry points take from it (a sequence given as NULL is a null pointer):
 //   K N {PREFIX REPEAT SUFFIX MAX_UNITS} x N       -> "key TEXT", or "refused RC TEXT"
 //   P MAX_TEMPLATE N {PREFIX REPEAT SUFFIX MAX_UNITS} x N
 //                                                  -> "pool LETTERS" (the whole pool, padding included) and per ladder "PERIOD
 //                                                     MAX_UNITS" and per strand "ALEN BLEN TRUNK_OFF BRANCH_OFF" (tab-separated;
 //                                                     two strands always, as stored), or "refused RC TEXT"
+//   Q MAX_TEMPLATE N {...} x N                     -> as P, with the limits of a plain reference on (1 .. MAX_TEMPLATE letters)
+//   B N_BUCKETS N KEY x N                          -> "order ITEM ..." and "off OFFSET ..." of bucket_order (a negative key: the
+//                                                     item is in no bucket)
 //   C CTX MEM_OK N_ITEMS N_LADDERS CAP NULL_TABLE PARAMS NULL_ARRAY
 //                                                  -> "call RC TEXT".  CTX, MEM_OK: 0|1; NULL_TABLE: which of prefix, repeat,
 //                                                     suffix, max_units is null (1..4, 0 none); PARAMS: NULL or MATCH,MISMATCH,
@@ -66,8 +69,8 @@ int main(int argc, char** argv) {
             printf("scoring %s\n", why ? why : "ok");
             k += 7;
         } else if ((!strcmp(argv[k], "K") && k + 1 < argc && k + 1 + 4 * atoi(argv[k + 1]) < argc) ||
-                   (!strcmp(argv[k], "P") && k + 2 < argc && k + 2 + 4 * atoi(argv[k + 2]) < argc)) {
-            const bool pack = argv[k][0] == 'P';
+                   ((!strcmp(argv[k], "P") || !strcmp(argv[k], "Q")) && k + 2 < argc && k + 2 + 4 * atoi(argv[k + 2]) < argc)) {
+            const bool pack = argv[k][0] != 'K', plain_limits = argv[k][0] == 'Q';
             const int at = k + (pack ? 3 : 2), n = atoi(argv[at - 1]);
             std::vector<const char*> cols[3];
             std::vector<int32_t> mu;
@@ -75,7 +78,7 @@ int main(int argc, char** argv) {
             std::string err, key;
             std::vector<ladder_host::LadderRecord> lad;
             ladder_host::Codes pool;
-            const int rc = pack ? ladder_host::pack_ladders(err, t, atoi(argv[k + 1]), lad, pool) : ladder_host::ladder_key(err, t, key);
+            const int rc = pack ? ladder_host::pack_ladders(err, t, atoi(argv[k + 1]), lad, pool, plain_limits) : ladder_host::ladder_key(err, t, key);
             if (rc) printf("refused %d %s\n", rc, err.c_str());
             else if (!pack) printf("key %s\n", key.c_str());
             else {
@@ -86,6 +89,19 @@ int main(int argc, char** argv) {
                 }
             }
             k = at + 4 * n;
+        } else if (!strcmp(argv[k], "B") && k + 2 < argc && k + 2 + atoi(argv[k + 2]) < argc) {
+            const int n = atoi(argv[k + 2]);
+            std::vector<long long> keys;               // exactly n entries: a read past them is the sanitizer's
+            for (int i = 0; i < n; ++i) keys.push_back(atoll(argv[k + 3 + i]));
+            std::vector<int32_t> order;
+            std::vector<int64_t> off;
+            ladder_host::bucket_order((size_t)n, (size_t)atoi(argv[k + 1]), [&](size_t i) { return keys[i]; }, order, off);
+            printf("order");
+            for (int32_t v : order) printf(" %d", v);
+            printf("\noff");
+            for (int64_t v : off) printf(" %lld", (long long)v);
+            printf("\n");
+            k += 3 + n;
         } else if (!strcmp(argv[k], "C") && k + 8 < argc) {
             const char* col[1] = {"A"};
             const int32_t mu[1] = {0};

@@ -1,8 +1,9 @@
-"""CPU: tredparse_amd/csrc/ladder_host.h, the host code sw_long.hip and the two CIGAR units share, through the stand-alone
+"""CPU: tredparse_amd/csrc/ladder_host.h, the HIP-free host code the five opt-in units share, through the stand-alone
 driver tests/ladder_host_main.cpp built with the address and undefined-behaviour sanitizers: the strand templates against a
-restatement in Python, the two refusals, the scoring check at every edge of its range, and what the CIGAR units' entry
-points take from it: the key of a ladder table, its records and letter pool, and every refusal's code and text."""
+restatement in Python, the two refusals, the scoring check at every edge of its range, the key of a ladder table, its
+records and letter pool, every refusal's code and text, and the counting sort of items into buckets."""
 import os
+import random
 import subprocess
 
 import pytest
@@ -152,6 +153,49 @@ def test_pack_refusals(run):
                                                                 "TREDGPU_MAX_LONG_TEMPLATE_LEN=4095"]
     assert run("P", 0, *flat([TWO[0], ("ACGT", "", "TGAC", 2)])) == ["refused -2 ladder 1: empty repeat"]
     assert run("P", 0, *flat([("ACGT", "CAG", "TGAC", -1)])) == ["refused -2 ladder 0: negative max_units"]
+
+
+def test_plain_reference_limits(run):
+    """The switch sw_long.hip packs with: a plain reference must have 1 .. max_template letters, in words of its own, and
+    nothing else changes."""
+    plain = lambda n: [("A" * n, "", "", 0)]
+    assert run("Q", 4095, *flat(plain(0))) == ["refused -2 ladder 0: reference length 0 not in [1,4095]"]
+    assert run("Q", 4095, *flat(plain(4096))) == ["refused -2 ladder 0: reference length 4096 not in [1,4095]"]
+    assert run("Q", 4095, *flat([TWO[0]] + plain(0))) == ["refused -2 ladder 1: reference length 0 not in [1,4095]"]
+    for ladders in (plain(1), plain(4095), TWO, LADDERS[:6]):
+        assert run("Q", 4095, *flat(ladders)) == expected_pool(ladders)
+    long_one = ("A" * 2048, "C", "G" * 2047, 1)                        # a ladder keeps the text it has without the switch
+    assert run("Q", 4095, *flat([long_one])) == run("P", 4095, *flat([long_one]))
+    assert run("P", 4095, *flat(plain(0))) == expected_pool(plain(0))  # without the switch an empty reference passes
+
+
+def bucket_order(run, n_buckets, keys):
+    out = run("B", n_buckets, len(keys), *keys)
+    assert len(out) == 2 and out[0].split()[0] == "order" and out[1].split()[0] == "off"
+    return [int(x) for x in out[0].split()[1:]], [int(x) for x in out[1].split()[1:]]
+
+
+RNG = random.Random(7)
+BUCKET_CASES = [
+    (3, []),                                                            # n = 0
+    (0, []),
+    (1, [0, 0, 0, 0, 0]),                                               # one bucket
+    (1, [0, -1, 0]),
+    (4, [-1, -7, -2147483648, -1]),                                     # all keys negative
+    (6, [5, -1, 0, 3, -2147483648, 3, 0, -1000, 5, 5, 2, -3, 0]),       # negatives of any size mixed in
+    (6, [RNG.randrange(6) for _ in range(1000)]),
+    (4200, [RNG.randrange(4200) for _ in range(1000)]),
+    (6, [RNG.randrange(-3, 6) for _ in range(1000)]),
+    (4200, [RNG.choice([-1, -2 ** 31, RNG.randrange(4200)]) for _ in range(1000)]),
+]
+
+
+@pytest.mark.parametrize("n_buckets,keys", BUCKET_CASES, ids=lambda v: str(v) if isinstance(v, int) else "n{}".format(len(v)))
+def test_bucket_order_is_a_stable_sort(run, n_buckets, keys):
+    order, off = bucket_order(run, n_buckets, keys)
+    kept = [k for k in range(len(keys)) if keys[k] >= 0]
+    assert order == sorted(kept, key=lambda k: keys[k])                 # (sorted is stable: the caller's order within a bucket)
+    assert off == [sum(1 for k in kept if keys[k] < b) for b in range(n_buckets + 1)]
 
 
 ARGS_TEXT = "n_items, n_ladders and cap must be positive"

@@ -85,6 +85,23 @@ EXPORTS = ("tredgpu_create", "tredgpu_destroy", "tredgpu_last_error", "tredgpu_s
            "tredgpu_inflate_walk", "tredgpu_inflater_fetch", "tredgpu_inflater_walk_ms", "tredgpu_inflater_host_out",
            "tredgpu_inflater_fetch_dense", "tredgpu_inflater_pinned_bytes", "tredgpu_inflater_walk_serial_regions")
 
+KERNEL_SW, KERNEL_TALLY, KERNEL_GRID = 0, 1, 2
+KERNEL_GRID_PREPARE, KERNEL_GRID_PAIRS, KERNEL_GRID_REDUCE, KERNEL_GRID_KDE = 3, 4, 5, 6
+KERNEL_CIGAR = 16               # include/tredcigar.h; tredgpu_get_timing's own series ends at 6
+KERNEL_CIGAR_LONG = 17          # tredlong_cigar_timing (include/tredlong.h): a selector of the binding's only
+KERNEL_SECOND = 18              # tredsecond_get_timing (include/tredsecond.h): calls of sw_secondary and their device time
+KERNEL_PILEUP = 19              # tredpileup_get_timing (include/tredpileup.h): calls of pileup and their device time
+
+
+# the timed opt-in units: (prefix, get-timing, reset-timing, KERNEL_* selector, last_error), in the order reset_timing has
+# always gone through them.  Context.close releases them (PREFIX_release) in this order too, tredlong first where it used
+# to be last: a release returns nothing and touches its own unit's state alone (tredlong_release also frees what
+# tredlong_sw_classify holds)
+SIDE_UNITS = (("tredlong", "tredlong_cigar_timing", "tredlong_cigar_reset_timing", KERNEL_CIGAR_LONG, "tredlong_last_error"),
+              ("tredcigar", "tredcigar_get_timing", "tredcigar_reset_timing", KERNEL_CIGAR, "tredcigar_last_error"),
+              ("tredsecond", "tredsecond_get_timing", "tredsecond_reset_timing", KERNEL_SECOND, "tredsecond_last_error"),
+              ("tredpileup", "tredpileup_get_timing", "tredpileup_reset_timing", KERNEL_PILEUP, "tredpileup_last_error"))
+
 _lib = None
 
 
@@ -106,38 +123,21 @@ def load():
     lib.tredgpu_sync.argtypes = [vp]
     lib.tredlong_sw_classify.argtypes = [vp, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                              C.POINTER(C.c_char_p), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, C.c_int32]
-    lib.tredlong_last_error.argtypes = []
-    lib.tredlong_last_error.restype = C.c_char_p
     lib.tredlong_sw_cigar.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                       vp, vp, vp, vp, i64, vp, vp, vp, C.POINTER(SwParams), i32, vp, vp, vp]
-    lib.tredlong_cigar_timing.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
-    lib.tredlong_cigar_reset_timing.argtypes = [vp]
-    lib.tredlong_release.argtypes = [vp]
-    lib.tredlong_release.restype = None
     lib.tredcigar_sw_cigar.argtypes = [vp, C.c_int, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                        vp, vp, vp, vp, i64, vp, vp, vp, C.POINTER(SwParams), i32, vp, vp, vp]
-    lib.tredcigar_get_timing.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
-    lib.tredcigar_reset_timing.argtypes = [vp]
-    lib.tredcigar_release.argtypes = [vp]
-    lib.tredcigar_release.restype = None
-    lib.tredcigar_last_error.argtypes = []
-    lib.tredcigar_last_error.restype = C.c_char_p
     lib.tredsecond_sw_second.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                          vp, vp, vp, vp, i64, vp, vp, vp, C.POINTER(SwParams), vp, vp]
-    lib.tredsecond_get_timing.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
-    lib.tredsecond_reset_timing.argtypes = [vp]
-    lib.tredsecond_release.argtypes = [vp]
-    lib.tredsecond_release.restype = None
-    lib.tredsecond_last_error.argtypes = []
-    lib.tredsecond_last_error.restype = C.c_char_p
     lib.tredpileup_pileup.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                       vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp]
-    lib.tredpileup_get_timing.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
-    lib.tredpileup_reset_timing.argtypes = [vp]
-    lib.tredpileup_release.argtypes = [vp]
-    lib.tredpileup_release.restype = None
-    lib.tredpileup_last_error.argtypes = []
-    lib.tredpileup_last_error.restype = C.c_char_p
+    for prefix, get_timing, reset_timing, _, last_error in SIDE_UNITS:
+        getattr(lib, get_timing).argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
+        getattr(lib, reset_timing).argtypes = [vp]
+        getattr(lib, prefix + "_release").argtypes = [vp]
+        getattr(lib, prefix + "_release").restype = None
+        getattr(lib, last_error).argtypes = []
+        getattr(lib, last_error).restype = C.c_char_p
     lib.tredgpu_get_stream.argtypes = [vp]
     lib.tredgpu_get_stream.restype = vp
     lib.tredgpu_version.restype = C.c_char_p
@@ -278,10 +278,8 @@ class Context:
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.tredcigar_release(self.h)
-            self.lib.tredsecond_release(self.h)
-            self.lib.tredpileup_release(self.h)
-            self.lib.tredlong_release(self.h)
+            for unit in SIDE_UNITS:
+                getattr(self.lib, unit[0] + "_release")(self.h)
             self.lib.tredgpu_destroy(self.h)
             self.h = None
 
@@ -640,31 +638,17 @@ class Context:
 
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")
-        self._chk_side(self.lib.tredlong_cigar_reset_timing(self.h), "tredlong_cigar_reset_timing failed",
-                       self.lib.tredlong_last_error)
-        self._chk_side(self.lib.tredcigar_reset_timing(self.h), "tredcigar_reset_timing failed", self.lib.tredcigar_last_error)
-        self._chk_side(self.lib.tredsecond_reset_timing(self.h), "tredsecond_reset_timing failed", self.lib.tredsecond_last_error)
-        self._chk_side(self.lib.tredpileup_reset_timing(self.h), "tredpileup_reset_timing failed", self.lib.tredpileup_last_error)
+        for _, _, reset_timing, _, last_error in SIDE_UNITS:
+            self._chk_side(getattr(self.lib, reset_timing)(self.h), reset_timing + " failed", getattr(self.lib, last_error))
 
     def get_timing(self, which):
         """(launches, total device ms) of kernel `which` since reset_timing (HIP events)."""
         n, ms = C.c_int64(0), C.c_double(0)
-        if which == KERNEL_CIGAR:
-            self._chk_side(self.lib.tredcigar_get_timing(self.h, C.byref(n), C.byref(ms)), "tredcigar_get_timing failed",
-                           self.lib.tredcigar_last_error)
-            return n.value, ms.value
-        if which == KERNEL_CIGAR_LONG:
-            self._chk_side(self.lib.tredlong_cigar_timing(self.h, C.byref(n), C.byref(ms)), "tredlong_cigar_timing failed",
-                           self.lib.tredlong_last_error)
-            return n.value, ms.value
-        if which == KERNEL_SECOND:
-            self._chk_side(self.lib.tredsecond_get_timing(self.h, C.byref(n), C.byref(ms)), "tredsecond_get_timing failed",
-                           self.lib.tredsecond_last_error)
-            return n.value, ms.value
-        if which == KERNEL_PILEUP:
-            self._chk_side(self.lib.tredpileup_get_timing(self.h, C.byref(n), C.byref(ms)), "tredpileup_get_timing failed",
-                           self.lib.tredpileup_last_error)
-            return n.value, ms.value
+        for _, get_timing, _, kernel, last_error in SIDE_UNITS:
+            if which == kernel:
+                self._chk_side(getattr(self.lib, get_timing)(self.h, C.byref(n), C.byref(ms)), get_timing + " failed",
+                               getattr(self.lib, last_error))
+                return n.value, ms.value
         self._chk(self.lib.tredgpu_get_timing(self.h, which, C.byref(n), C.byref(ms)), "tredgpu_get_timing")
         return n.value, ms.value
 
@@ -678,14 +662,6 @@ class Context:
     def pe_kde(self, mem, units, n_units, global_lens, n_global_total, pdf_out, status_out):
         self._chk(self.lib.tredgpu_pe_kde(self.h, mem, _ptr(units), n_units, _ptr(global_lens),
                                           n_global_total, _ptr(pdf_out), _ptr(status_out)), "tredgpu_pe_kde")
-
-
-KERNEL_SW, KERNEL_TALLY, KERNEL_GRID = 0, 1, 2
-KERNEL_GRID_PREPARE, KERNEL_GRID_PAIRS, KERNEL_GRID_REDUCE, KERNEL_GRID_KDE = 3, 4, 5, 6
-KERNEL_CIGAR = 16               # include/tredcigar.h; tredgpu_get_timing's own series ends at 6
-KERNEL_CIGAR_LONG = 17          # tredlong_cigar_timing (include/tredlong.h): a selector of the binding's only
-KERNEL_SECOND = 18              # tredsecond_get_timing (include/tredsecond.h): calls of sw_secondary and their device time
-KERNEL_PILEUP = 19              # tredpileup_get_timing (include/tredpileup.h): calls of pileup and their device time
 
 
 def default_sw_params(clip=False, max_read_len=0):

@@ -1,7 +1,8 @@
-// ladder_host.h -- the host code the opt-in units (sw_long.hip, and through cigar_unit.h sw_cigar.hip and
-// sw_cigar_long.hip) share: base codes, the strand templates of a ladder, the error-text helper and the scoring-range
-// check; for the two CIGAR units also the key of a ladder table, its packing into records and a letter pool, and the
-// argument checks of their entry points.  Plain C++17, nothing from HIP (tests/ladder_host_main.cpp runs it under ASan).
+// ladder_host.h -- the HIP-free half of what the five opt-in units (sw_long.hip, sw_cigar.hip, sw_cigar_long.hip,
+// sw_second.hip, pileup.hip) share; side_unit.h, which includes it, is the half that needs HIP.  Base codes, the strand
+// templates of a ladder, the error-text helper and the scoring-range check; the key of a ladder table and its packing
+// into records and a letter pool; the argument checks of the entry points; the stable counting sort of a call's items
+// into buckets.  Plain C++17 (tests/ladder_host_main.cpp runs it under ASan).
 //
 // capi.hip keeps its own copy of these functions (base_code / encode / revcomp and the construction in
 // tredgpu_set_ladders) on purpose: it belongs to the sources whose hash the records under profiles/ carry (SRC_HASH in
@@ -103,7 +104,7 @@ inline const char* scoring_refusal(const tredgpu_sw_params& p, bool with_flank) 
                       : "scoring out of the supported range (match 1..8, mismatch 0..16, 1 <= gap_extend <= gap_open <= 16)";
 }
 
-// ---- what the two CIGAR units (cigar_unit.h) share ---------------------------------------------------------------------
+// ---- the ladder table and the argument checks ------------------------------------------------------------------------------
 
 // a ladder table as the entry points take it
 struct Table { int32_t n; const char* const *prefix, *const *repeat, *const *suffix; const int32_t* max_units; };
@@ -127,8 +128,10 @@ inline int ladder_key(std::string& err, const Table& t, std::string& key) {
 }
 
 // the table as records and one pool of letters: per ladder and strand the trunk, then the branch, and 16 bytes of N behind
-// the last.  max_template: the longest template a ladder may have (0: the items are checked on the device instead)
-inline int pack_ladders(std::string& err, const Table& t, int max_template, std::vector<LadderRecord>& lad, Codes& pool) {
+// the last.  max_template: the longest template a ladder may have (0: the items are checked on the device instead).
+// plain_limits: a plain reference (max_units == 0) must have 1 .. max_template letters and is refused in words of its own
+inline int pack_ladders(std::string& err, const Table& t, int max_template, std::vector<LadderRecord>& lad, Codes& pool,
+                        bool plain_limits = false) {
     lad.assign((size_t)t.n, LadderRecord());
     pool.clear();
     auto append = [&pool](const Codes& v) {
@@ -142,6 +145,8 @@ inline int pack_ladders(std::string& err, const Table& t, int max_template, std:
         if (const char* why = build_strands(t.prefix[i], t.repeat[i], t.suffix[i], t.max_units[i], S))
             return fail(err, -2, "ladder %d: %s", i, why);
         const size_t T = (size_t)S.alen[0] + S.blen[0] + (size_t)S.period * S.max_units;
+        if (plain_limits && S.max_units == 0 && (T < 1 || T > (size_t)max_template))
+            return fail(err, -2, "ladder %d: reference length %zu not in [1,%d]", i, T, max_template);
         if (max_template > 0 && T > (size_t)max_template)
             return fail(err, -2, "ladder %d: longest template %zu exceeds TREDGPU_MAX_LONG_TEMPLATE_LEN=%d", i, T, max_template);
         d.period = S.period; d.max_units = S.max_units;
@@ -182,6 +187,20 @@ inline int reads_refusal(std::string& err, const int64_t* read_off, const int32_
             return fail(err, -2, "item %zu: its read does not lie inside packed[0 .. read_off[n_items])", k);
     }
     return 0;
+}
+
+// The stable counting sort of n items into n_buckets buckets: key(k) is item k's bucket, or negative for an item that is
+// in none.  order: the items bucket after bucket, in the caller's order within one; off: the n_buckets + 1 offsets into it.
+template <class Key>
+void bucket_order(size_t n, size_t n_buckets, Key key, std::vector<int32_t>& order, std::vector<int64_t>& off) {
+    off.assign(n_buckets + 1, 0);
+    for (size_t k = 0; k < n; ++k)
+        if (key(k) >= 0) off[(size_t)key(k) + 1] += 1;
+    for (size_t b = 0; b < n_buckets; ++b) off[b + 1] += off[b];
+    order.resize((size_t)off[n_buckets]);
+    std::vector<int64_t> fill(off.begin(), off.end() - 1);
+    for (size_t k = 0; k < n; ++k)
+        if (key(k) >= 0) order[(size_t)fill[(size_t)key(k)]++] = (int32_t)k;
 }
 
 }  // namespace ladder_host

@@ -1,7 +1,7 @@
 // pileup.hip -- per-allele evidence from per-read alignments (tredpileup_pileup, include/tredpileup.h): the items of a
 // group -- (read, template, fields, CIGAR operations) as tredcigar_sw_cigar takes and returns them -- counted column by
 // column of the group's forward template into int32 [n_groups][stride][8].  A unit of its own, outside the source hash
-// the profiles are tied to (csrc/Makefile); the host harness is cigar_unit.h's and ladder_host.h's.
+// the profiles are tied to (csrc/Makefile); the harness is side_unit.h's and ladder_host.h's.
 //
 // Two kernels per call.
 //   * validate_kernel, one lane per item: every refusal of the header that an item can be given on its own (indices,
@@ -22,12 +22,12 @@
 #include <climits>
 #include <cstring>
 
-#include "cigar_unit.h"
+#include "side_unit.h"
 #include "../../include/tredlong.h"
 #include "../../include/tredpileup.h"
 
 namespace {
-using namespace cigar_unit;
+using namespace side_unit;
 
 thread_local std::string g_pileup_error;   // the text of tredpileup_last_error()
 
@@ -54,20 +54,17 @@ struct PileArgs {
     int32_t* pre;              // [n_items]: the status of validate_kernel
     int32_t* out_counts;       // [n_groups][stride][CH]
     int32_t* out_status;
+    const uint8_t* letters;    // fill_table's other fields, which no kernel of this unit reads
+    int32_t match, mismatch, gap_open, gap_extend;
 };
-
-// the length of template tpl (in range) of a ladder; both strands have the same
-__device__ __forceinline__ int template_len(const LadderRecord& d, int tpl) {
-    return d.alen[0] + (d.max_units > 0 ? d.period * (tpl / 2 + 1) : 0) + d.blen[0];
-}
 
 __device__ int validate(const PileArgs& a, int64_t item) {
     const int g = a.item_group[item];
     if (g < 0 || g >= a.n_groups) return TREDGPU_PILEUP_BAD_ITEM;
     const int lad = a.item_ladder[item], tpl = a.item_template[item];
     if (lad < 0 || lad >= a.n_ladders) return TREDGPU_PILEUP_BAD_ITEM;
-    const LadderRecord d = a.ladders[lad];
-    if (tpl < 0 || tpl >= (d.max_units > 0 ? 2 * d.max_units : 1)) return TREDGPU_PILEUP_BAD_ITEM;
+    const LadderRecord d = a.ladders[lad];                           // (a copy, and no field by strand: see template_of)
+    if (tpl < 0 || tpl >= n_templates(d)) return TREDGPU_PILEUP_BAD_ITEM;
     const int tlen = template_len(d, tpl), L = a.read_len[item];
     if (L > TREDGPU_MAX_LONG_READ_LEN || tlen > TREDGPU_MAX_LONG_TEMPLATE_LEN) return TREDGPU_PILEUP_TOO_LONG;
     const int16_t* fl = a.fields + (size_t)item * 5;
@@ -178,8 +175,7 @@ __global__ __launch_bounds__(THREADS) void pileup_kernel(PileArgs a) {
     }
 }
 
-// st: the six item inputs, ops, n_ops and out_status; the rest is the unit's
-struct State : StateBase { Dev group, order, goff, pre, counts; };
+struct State : StateBase {};
 Registry<State> g_states;
 
 }  // namespace
@@ -222,39 +218,19 @@ int tredpileup_pileup(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* pr
     if ((rc = set_ladders(err, s, st, t, 0))) return rc;           // (a template beyond the limit is the item's TOO_LONG)
 
     // the items by group, in the caller's order within a group; an item whose group is out of range is in no list
-    std::vector<int64_t> goff((size_t)n_groups + 1, 0);
-    auto in_range = [&](size_t k) { return item_group[k] >= 0 && item_group[k] < n_groups; };
-    for (size_t k = 0; k < n; ++k)
-        if (in_range(k)) goff[(size_t)item_group[k] + 1] += 1;
-    for (int g = 0; g < n_groups; ++g) goff[g + 1] += goff[g];
-    std::vector<int32_t> order((size_t)goff[n_groups] + 1);
-    {
-        std::vector<int64_t> fill(goff.begin(), goff.end() - 1);
-        for (size_t k = 0; k < n; ++k)
-            if (in_range(k)) order[(size_t)fill[item_group[k]]++] = (int32_t)k;
-    }
-
-    const size_t sizes[9] = {(size_t)read_off[n] * 4, (n + 1) * 8, n * 4, n * 4, n * 4, n * 10, n * (size_t)cap * 4, n * 4, n * 4};
-    const void* src[9] = {packed, read_off, read_len, item_ladder, item_template, fields, ops, n_ops, nullptr};
-    for (int k = 0; k < 9; ++k)
-        if ((rc = ensure(err, s.st[k], sizes[k], st))) return rc;
-    Dev* own[5] = {&s.group, &s.order, &s.goff, &s.pre, &s.counts};
-    const size_t own_sizes[5] = {n * 4, order.size() * 4, goff.size() * 8, n * 4, cells * 4};
-    const void* own_src[5] = {item_group, order.data(), goff.data(), nullptr, nullptr};
-    for (int k = 0; k < 5; ++k)
-        if ((rc = ensure(err, *own[k], own_sizes[k], st))) return rc;
-    for (int k = 0; k < 9; ++k)
-        if (src[k] && sizes[k]) CIGAR_UNIT_CHK(err, hipMemcpyAsync(s.st[k].p, src[k], sizes[k], hipMemcpyHostToDevice, st));
-    for (int k = 0; k < 5; ++k)
-        if (own_src[k]) CIGAR_UNIT_CHK(err, hipMemcpyAsync(own[k]->p, own_src[k], own_sizes[k], hipMemcpyHostToDevice, st));
+    std::vector<int32_t> order;
+    std::vector<int64_t> goff;
+    bucket_order(n, (size_t)n_groups, [&](size_t k) { return item_group[k] < n_groups ? item_group[k] : -1; }, order, goff);
 
     PileArgs a{};
-    a.packed = (const uint32_t*)s.st[0].p; a.read_off = (const int64_t*)s.st[1].p; a.read_len = (const int32_t*)s.st[2].p;
-    a.item_ladder = (const int32_t*)s.st[3].p; a.item_template = (const int32_t*)s.st[4].p; a.fields = (const int16_t*)s.st[5].p;
-    a.ops = (const uint32_t*)s.st[6].p; a.n_ops = (const int32_t*)s.st[7].p; a.out_status = (int32_t*)s.st[8].p;
-    a.item_group = (const int32_t*)s.group.p; a.order = (const int32_t*)s.order.p; a.goff = (const int64_t*)s.goff.p;
-    a.pre = (int32_t*)s.pre.p; a.out_counts = (int32_t*)s.counts.p;
-    a.ladders = (const LadderRecord*)s.ladders.p; a.n_ladders = s.n_ladders;
+    fill_table(a, s, any_scoring);
+    const std::vector<Array> arrays = {
+        arr_in(a.packed, packed, (size_t)read_off[n]), arr_in(a.read_off, read_off, n + 1), arr_in(a.read_len, read_len, n),
+        arr_in(a.item_ladder, item_ladder, n), arr_in(a.item_template, item_template, n), arr_in(a.fields, fields, n * 5),
+        arr_in(a.ops, ops, n * (size_t)cap), arr_in(a.n_ops, n_ops, n), arr_in(a.item_group, item_group, n),
+        arr_in(a.order, order.data(), order.size()), arr_in(a.goff, goff.data(), goff.size()), arr_scratch(a.pre, n),
+        arr_out(a.out_counts, out_counts, cells), arr_out(a.out_status, out_status, n)};
+    if ((rc = stage(err, s, st, arrays))) return rc;
     a.n_items = n_items; a.cap = cap; a.n_groups = n_groups; a.stride = stride; a.ntile = (stride + TILE - 1) / TILE;
 
     if ((rc = timed_begin(err, s, st))) return rc;
@@ -262,17 +238,14 @@ int tredpileup_pileup(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* pr
     const int64_t n_work = (int64_t)n_groups * a.ntile;
     hipLaunchKernelGGL(pileup_kernel, dim3((unsigned)std::min<int64_t>(n_work, MAX_BLOCKS)), dim3(THREADS), 0, st, a);
     if ((rc = timed_end(err, s, st))) return rc;
-    CIGAR_UNIT_CHK(err, hipMemcpyAsync(out_counts, a.out_counts, cells * 4, hipMemcpyDeviceToHost, st));
-    CIGAR_UNIT_CHK(err, hipMemcpyAsync(out_status, a.out_status, n * 4, hipMemcpyDeviceToHost, st));
-    CIGAR_UNIT_CHK(err, hipStreamSynchronize(st));                 // (order and goff are read by the copies above until here)
-    return 0;
+    return read_back(err, s, st, arrays);                          // (order and goff are read by their copies until the stream is drained)
 }
 
 int tredpileup_get_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms) { return timing(g_pileup_error, g_states, ctx, launches, total_ms, false); }
 
 int tredpileup_reset_timing(tredgpu_ctx* ctx) { return timing(g_pileup_error, g_states, ctx, nullptr, nullptr, true); }
 
-void tredpileup_release(tredgpu_ctx* ctx) { release(g_states, ctx, {&State::group, &State::order, &State::goff, &State::pre, &State::counts}); }
+void tredpileup_release(tredgpu_ctx* ctx) { release(g_states, ctx, {}); }
 
 const char* tredpileup_last_error(void) { return g_pileup_error.c_str(); }
 

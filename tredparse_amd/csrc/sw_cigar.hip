@@ -158,7 +158,7 @@ __global__ __launch_bounds__(64) void cigar_wide_kernel(CigarArgs a) {
     }
 }
 
-// ---- host side (cigar_unit.h) -------------------------------------------------------------------------------------------
+// ---- host side (side_unit.h) --------------------------------------------------------------------------------------------
 thread_local std::string g_cigar_error;
 
 struct State : StateBase { Dev narrow_plane, wide_plane, wide_rows, wide_list; };
@@ -190,7 +190,12 @@ int tredcigar_sw_cigar(tredgpu_ctx* ctx, int mem, int32_t n_ladders, const char*
     const size_t n = (size_t)n_items;
     CigarArgs a{};
     fill_args(a, *s, packed, read_off, read_len, n_items, item_ladder, item_template, fields, *p, cap, out_ops, out_n_ops, out_status);
-    if (host && ((rc = reads_refusal(err, read_off, read_len, n, -1)) || (rc = stage(err, *s, st, a)))) return rc;
+    std::vector<Array> arrays;                                   // device memory: nothing is staged
+    if (host) {
+        if ((rc = reads_refusal(err, read_off, read_len, n, -1))) return rc;
+        arrays = host_arrays(a);
+        if ((rc = stage(err, *s, st, arrays))) return rc;
+    }
     const int blocks = (int)std::min<size_t>((n + 63) / 64, NARROW_MAX_LANES / 64);
     if ((rc = ensure(err, s->narrow_plane, (size_t)blocks * 64 * NARROW_PLANE, st))) return rc;
     if ((rc = ensure(err, s->wide_plane, (size_t)WIDE_LANES * WIDE_PLANE, st))) return rc;
@@ -198,16 +203,16 @@ int tredcigar_sw_cigar(tredgpu_ctx* ctx, int mem, int32_t n_ladders, const char*
     if ((rc = ensure(err, s->wide_list, (n + 1) * sizeof(int32_t), st))) return rc;
     a.wide_list = (int32_t*)s->wide_list.p;
     a.wide_rows = (int16_t*)s->wide_rows.p;
-    CIGAR_UNIT_CHK(err, hipMemsetAsync(a.wide_list + n, 0, sizeof(int32_t), st));
-    CIGAR_UNIT_CHK(err, hipMemsetAsync(a.out_n_ops, 0, n * sizeof(int32_t), st));
+    SIDE_UNIT_CHK(err, hipMemsetAsync(a.wide_list + n, 0, sizeof(int32_t), st));
+    SIDE_UNIT_CHK(err, hipMemsetAsync(a.out_n_ops, 0, n * sizeof(int32_t), st));
     if ((rc = timed_begin(err, *s, st))) return rc;
     a.plane = (uint8_t*)s->narrow_plane.p;
     hipLaunchKernelGGL(cigar_narrow_kernel, dim3(blocks), dim3(64), 0, st, a);
-    CIGAR_UNIT_CHK(err, hipGetLastError());
+    SIDE_UNIT_CHK(err, hipGetLastError());
     a.plane = (uint8_t*)s->wide_plane.p;
     hipLaunchKernelGGL(cigar_wide_kernel, dim3(1), dim3(WIDE_LANES), 0, st, a);
     if ((rc = timed_end(err, *s, st))) return rc;
-    return host ? read_back(err, st, a, out_ops, out_n_ops, out_status) : 0;
+    return host ? read_back(err, *s, st, arrays) : 0;
 }
 
 int tredcigar_get_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms) { return timing(g_cigar_error, g_states, ctx, launches, total_ms, false); }

@@ -26,6 +26,7 @@
 
 namespace tredgpu {
 extern thread_local std::string g_long_error;   // sw_long.hip: the text of tredlong_last_error()
+void long_classify_release(tredgpu_ctx* ctx);   // sw_long.hip: what tredlong_sw_classify holds for the context
 }
 
 namespace {
@@ -41,15 +42,6 @@ struct LongCigarArgs : Args {  // plane: [slot][slot_bytes]
 
 constexpr int ROW = 4100;                 // entries per row array: e <= refLen + 1, edge <= refLen
 constexpr int LNEG = -(1 << 29);
-
-__device__ __forceinline__ int wave_incl_max(int x, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, (unsigned)d, 64);
-        if (lane >= d) x = max(x, y);
-    }
-    return x;
-}
 
 // the passes and the traceback of an item the decode accepted, on one wavefront; every lane returns the status
 __device__ int long_cigar_item(const LongCigarArgs& a, int64_t item, const Item& it, uint8_t* plane, int16_t* hb, int16_t* eb,
@@ -156,7 +148,7 @@ __global__ __launch_bounds__(64) void cigar_long_kernel(LongCigarArgs a) {
     }
 }
 
-// ---- host side (cigar_unit.h) -------------------------------------------------------------------------------------------
+// ---- host side (side_unit.h) --------------------------------------------------------------------------------------------
 struct State : StateBase { Dev plane; };   // sized exactly: plan.total() is what the slots of a launch address
 Registry<State> g_states;
 
@@ -185,21 +177,25 @@ int tredlong_sw_cigar(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* pr
     const cigar_long_plan::Plan plan = cigar_long_plan::plan(fields, n_items);
     LongCigarArgs a{};
     fill_args(a, *s, packed, read_off, read_len, n_items, item_ladder, item_template, fields, *p, cap, out_ops, out_n_ops, out_status);
-    if ((rc = stage(err, *s, st, a))) return rc;
+    const std::vector<Array> arrays = host_arrays(a);
+    if ((rc = stage(err, *s, st, arrays))) return rc;
     if ((rc = ensure(err, s->plane, plan.total(), st, false))) return rc;
     a.plane = (uint8_t*)s->plane.p;
     a.slot_bytes = plan.slot_bytes;
-    CIGAR_UNIT_CHK(err, hipMemsetAsync(a.out_n_ops, 0, n * sizeof(int32_t), st));
+    SIDE_UNIT_CHK(err, hipMemsetAsync(a.out_n_ops, 0, n * sizeof(int32_t), st));
     if ((rc = timed_begin(err, *s, st))) return rc;
     hipLaunchKernelGGL(cigar_long_kernel, dim3(plan.slots), dim3(64), 0, st, a);
     if ((rc = timed_end(err, *s, st))) return rc;
-    return read_back(err, st, a, out_ops, out_n_ops, out_status);
+    return read_back(err, *s, st, arrays);
 }
 
 int tredlong_cigar_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms) { return timing(g_long_error, g_states, ctx, launches, total_ms, false); }
 
 int tredlong_cigar_reset_timing(tredgpu_ctx* ctx) { return timing(g_long_error, g_states, ctx, nullptr, nullptr, true); }
 
-void tredlong_release(tredgpu_ctx* ctx) { release(g_states, ctx, {&State::plane}); }
+void tredlong_release(tredgpu_ctx* ctx) {
+    release(g_states, ctx, {&State::plane});
+    tredgpu::long_classify_release(ctx);
+}
 
 }  // extern "C"

@@ -19,18 +19,27 @@
 //    swept from it, and the trunk resumes: (|trunk| + max_units * |suffix|) columns per strand instead of the
 //    O(max_units^2) of separate alignments.
 // No pruning: every template of both strands is aligned (the path serves rare reads; the per-template dump needs all).
-#include <algorithm>
-#include <cstring>
-
-#include "ladder_host.h"
-#include "tredgpu_internal.h"
+#include "side_unit.h"
 #include "../../include/tredlong.h"
 
 namespace tredgpu {
 namespace {
+using namespace side_unit;
 
-struct LongLadder {
-    LadderDesc d;   // tredgpu_set_ladders' layout (kmer fields unused)
+struct LongArgs {
+    const LadderRecord* ladders;
+    const uint8_t* letters;
+    int32_t n_ladders;
+    int32_t match, mismatch, gap_open, gap_extend;
+    const uint32_t* packed;
+    const int64_t* read_off;
+    const int32_t *read_len, *read_ladder;
+    int32_t flank, clip;
+    const int32_t* list;       // the reads of this launch's row class
+    int32_t n_list;
+    uint8_t* out_tag;
+    int16_t *out_h, *out_score, *out_dump;
+    int32_t dump_templates;
 };
 
 constexpr int LNEG = -(1 << 30);
@@ -45,10 +54,12 @@ __device__ __forceinline__ long long max64(long long a, long long b) { return a 
 __device__ __forceinline__ long long shfl_up64(long long v, int d) { return __shfl_up(v, (unsigned)d, 64); }
 __device__ __forceinline__ long long shfl_xor64(long long v, int d) { return __shfl_xor(v, d, 64); }
 
-// Ladder letters: 8 per 32-bit word (tredgpu_set_ladders); wave-uniform index.
-__device__ __forceinline__ int ladder_letter(const uint32_t* seqw, int word_off, int idx) {
-    const uint32_t w = seqw[word_off + (idx >> 3)];
-    return (int)((w >> ((idx & 7) * 4)) & 7u);
+// Ladder letters: one per byte of the pool; the index is wave-uniform, and the letter comes out of the aligned word that
+// holds its byte (the pool ends in 16 bytes of padding, and its buffer begins on a word boundary).
+__device__ __forceinline__ int ladder_letter(const uint8_t* letters, int off, int idx) {
+    const int at = off + idx;
+    const uint32_t w = ((const uint32_t*)letters)[at >> 2];
+    return (int)((w >> ((at & 3) * 8)) & 7u);
 }
 
 template <int R>
@@ -90,14 +101,7 @@ __device__ __forceinline__ void long_column(const LongRows<R>& J, long long (&H)
         E[r] = max64(E[r], q);                                // E~ for the next column (fed from H without F)
     }
     // exclusive max scan over the 64 lanes: F~ entering this lane from the rows above it
-    long long x = run;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long y = shfl_up64(x, d);
-        if (lane >= d) x = max64(x, y);
-    }
-    long long F = shfl_up64(x, 1);
-    if (lane == 0) F = mk(LNEG, 0);
+    long long F = wave_excl_max(run, lane, mk(LNEG, 0));
     int m = LNEG;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -125,29 +129,16 @@ __device__ __forceinline__ void long_column(const LongRows<R>& J, long long (&H)
     }
 }
 
-__device__ __forceinline__ uint32_t score_lut(int let, const tredgpu_sw_params& p) {
-    uint32_t lut = 0;
-    for (int k = 0; k < 6; ++k) {
-        int s;
-        if (k == 5) s = -16;                            // padding row (see long_column)
-        else if (k == 4 || let > 3) s = 0;              // N on either side scores 0 (ssw_wrap.py:162-167)
-        else s = k == let ? p.match : -p.mismatch;
-        lut |= (uint32_t)(s + 16) << (5 * k);
-    }
-    return lut;
-}
-
 template <int R>
-__global__ __launch_bounds__(64) void sw_long_kernel(SwArgs a, const LongLadder* lads, const int2* list, const int32_t* count) {
+__global__ __launch_bounds__(64) void sw_long_kernel(LongArgs a) {
     // the trunk state parked while a template's suffix is swept: H and E of every row
     __shared__ long long park[2 * R * 64];
     const int lane = __lane_id();
-    const int n = *count;
-    const int ge = a.p.gap_extend, c0 = a.p.gap_open - a.p.gap_extend, flank = a.p.flank;
+    const int n = a.n_list;
+    const int ge = a.gap_extend, c0 = a.gap_open - a.gap_extend, flank = a.flank;
     for (int it = blockIdx.x; it < n; it += gridDim.x) {
-        const int2 ent = list[it];
-        const int64_t rd = ent.x;
-        const LadderDesc& ld = lads[ent.y].d;
+        const int64_t rd = a.list[it];
+        const LadderRecord& ld = a.ladders[a.read_ladder[rd]];       // (the host has checked the index)
         const int L = a.read_len[rd];
         if (L > 64 * R || L > TREDGPU_MAX_LONG_READ_LEN) {   // out of this path's range: flagged, not aligned
             if (lane == 0) { a.out_tag[rd] = TREDGPU_TAG_INVALID; a.out_h[rd] = 0; a.out_score[rd] = 0; }
@@ -164,14 +155,15 @@ __global__ __launch_bounds__(64) void sw_long_kernel(SwArgs a, const LongLadder*
             for (int r = 0; r < R; ++r) {
                 const int i = J.row0 + r;
                 int code = 5;
-                if (i < L) code = ((rec[nb + (i >> 5)] >> (i & 31)) & 1u) ? 4 : (int)((rec[i >> 4] >> ((i & 15) * 2)) & 3u);
+                if (i < L) code = read_code(rec, nb, i);
                 J.code[r >> 2] |= (uint32_t)(5 * code) << ((r & 3) * 8);
             }
         }
-        const int period = ld.period, max_units = ld.max_units;
-        const int mu_rept = a.p.clip ? (L + period - 1) / period : max_units;
+        const int max_units = ld.max_units, n_strands = max_units > 0 ? 2 : 1;
+        const int period = max_units > 0 ? ld.period : 1;           // a plain reference: one template, one unit column wide
+        const int mu_rept = a.clip ? (L + period - 1) / period : max_units;
         int bestS = 0, bestU = 0, bestTag = TREDGPU_TAG_NONE;   // arg-max (score, -units), first in db order
-        for (int s = 0; s < ld.n_strands; ++s) {
+        for (int s = 0; s < n_strands; ++s) {
             const int alen = ld.alen[s], blen = ld.blen[s];
             const int ncols = alen + period * max_units;
             long long H[R], E[R];
@@ -181,7 +173,7 @@ __global__ __launch_bounds__(64) void sw_long_kernel(SwArgs a, const LongLadder*
             int u = max_units > 0 ? 1 : 0;
             int next_end = max_units > 0 ? alen + period - 1 : alen - 1;
             for (int col = 0; col < ncols; ++col) {
-                long_column<R>(J, H, E, T, col, score_lut(ladder_letter(a.seqw, ld.trunk_off[s], col), a.p), ge, c0);
+                long_column<R>(J, H, E, T, col, score_lut(ladder_letter(a.letters, ld.trunk_off[s], col), a.match, a.mismatch), ge, c0);
                 if (col != next_end) continue;
                 // ---- template u ends here on the trunk: sweep its suffix from the parked trunk state ----
                 LongBest B = T;
@@ -189,7 +181,7 @@ __global__ __launch_bounds__(64) void sw_long_kernel(SwArgs a, const LongLadder*
 #pragma unroll
                     for (int r = 0; r < R; ++r) { park[(2 * r) * 64 + lane] = H[r]; park[(2 * r + 1) * 64 + lane] = E[r]; }
                     for (int j = 0; j < blen; ++j)
-                        long_column<R>(J, H, E, B, col + 1 + j, score_lut(ladder_letter(a.seqw, ld.branch_off[s], j), a.p), ge, c0);
+                        long_column<R>(J, H, E, B, col + 1 + j, score_lut(ladder_letter(a.letters, ld.branch_off[s], j), a.match, a.mismatch), ge, c0);
 #pragma unroll
                     for (int r = 0; r < R; ++r) { H[r] = park[(2 * r) * 64 + lane]; E[r] = park[(2 * r + 1) * 64 + lane]; }
                 }
@@ -254,36 +246,22 @@ __global__ __launch_bounds__(64) void sw_long_kernel(SwArgs a, const LongLadder*
 }  // namespace
 }  // namespace tredgpu
 
-// ---- C entry points (include/tredlong.h) ----------------------------------------------------------------------
+// ---- C entry points (include/tredlong.h); host side: side_unit.h ---------------------------------------------------
 using namespace tredgpu;
-using namespace ladder_host;
+using namespace side_unit;
 
 namespace tredgpu {
 thread_local std::string g_long_error;   // the text of tredlong_last_error(); sw_cigar_long.hip writes it as well
 }
 
 namespace {
-
-// device buffers of one call, released on every way out
-struct DevBufs {
-    std::vector<void*> p;
-    ~DevBufs() { for (void* q : p) (void)hipFree(q); }
-    template <typename T>
-    hipError_t get(T** out, size_t n) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n * sizeof(T), 16));
-        if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
-        return e;
-    }
-};
-
-#define LCHK(expr)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return fail(g_long_error, -10, "%s: %s", #expr, hipGetErrorString(e_));    \
-    } while (0)
-
+struct State : StateBase {};
+Registry<State> g_states;
 }  // namespace
+
+namespace tredgpu {
+void long_classify_release(tredgpu_ctx* ctx) { release(g_states, ctx, {}); }   // tredlong_release's half (sw_cigar_long.hip)
+}
 
 extern "C" {
 
@@ -294,118 +272,62 @@ int tredlong_sw_classify(tredgpu_ctx* ctx, int32_t n_ladders, const char* const*
                              const int64_t* read_off, const int32_t* read_len, int64_t n_reads, const int32_t* read_ladder,
                              const tredgpu_sw_params* p, uint8_t* out_tag, int16_t* out_h, int16_t* out_score,
                              int16_t* out_dump, int32_t dump_templates) {
-    g_long_error.clear();
-    if (!ctx || !p) return fail(g_long_error, -2, "ctx or params is NULL");
-    if (n_ladders <= 0 || !prefix || !repeat || !suffix || !max_units) return fail(g_long_error, -2, "bad ladder arguments");
-    if (n_reads < 0) return fail(g_long_error, -2, "negative n_reads");
+    std::string& err = g_long_error;
+    err.clear();
+    if (!ctx || !p) return fail(err, -2, "ctx or params is NULL");
+    if (n_ladders <= 0 || !prefix || !repeat || !suffix || !max_units) return fail(err, -2, "bad ladder arguments");
+    if (n_reads < 0) return fail(err, -2, "negative n_reads");
     if (n_reads > 0 && (!packed || !read_off || !read_len || !read_ladder || !out_tag || !out_h || !out_score))
-        return fail(g_long_error, -2, "NULL array argument");
-    if (out_dump && dump_templates <= 0) return fail(g_long_error, -2, "dump_templates must be > 0 with out_dump");
-    if (const char* why = scoring_refusal(*p, true)) return fail(g_long_error, -2, "%s", why);
-    // ladders: the layout of tredgpu_set_ladders (letters 8 per word, every segment on a word boundary)
-    std::vector<uint32_t> seq;
-    auto append = [&seq](const Codes& v) {
-        const int off = (int)seq.size();
-        seq.resize(seq.size() + (v.size() + 7) / 8 + 1, 0x44444444u);
-        for (size_t i = 0; i < v.size(); ++i) {
-            uint32_t& w = seq[off + i / 8];
-            w = (w & ~(0xFu << ((i % 8) * 4))) | ((uint32_t)v[i] << ((i % 8) * 4));
-        }
-        return off;
-    };
-    std::vector<LongLadder> lad((size_t)n_ladders);
-    Strands S;
-    for (int i = 0; i < n_ladders; ++i) {
-        LadderDesc& d = lad[i].d;
-        memset(&lad[i], 0, sizeof lad[i]);
-        if (const char* why = build_strands(prefix[i], repeat[i], suffix[i], max_units[i], S))
-            return fail(g_long_error, -2, "ladder %d: %s", i, why);
-        const size_t T = (size_t)S.alen[0] + S.blen[0] + (size_t)S.period * S.max_units;
-        if (S.max_units == 0 && (T < 1 || T > TREDGPU_MAX_LONG_TEMPLATE_LEN))
-            return fail(g_long_error, -2, "ladder %d: reference length %zu not in [1,%d]", i, T, TREDGPU_MAX_LONG_TEMPLATE_LEN);
-        if (T > TREDGPU_MAX_LONG_TEMPLATE_LEN)
-            return fail(g_long_error, -2, "ladder %d: longest template %zu exceeds TREDGPU_MAX_LONG_TEMPLATE_LEN=%d", i, T,
-                        TREDGPU_MAX_LONG_TEMPLATE_LEN);
-        for (int s = 0; s < S.n_strands; ++s) {
-            d.alen[s] = S.alen[s];
-            d.blen[s] = S.blen[s];
-            d.trunk_off[s] = append(S.trunk[s]);
-            d.branch_off[s] = append(S.branch[s]);
-        }
-        d.period = S.max_units > 0 ? S.period : 1;     // a plain reference: one template, one unit column wide
-        d.max_units = S.max_units;
-        d.n_strands = S.n_strands;
-    }
-    seq.resize(seq.size() + 4, 0x44444444u);
+        return fail(err, -2, "NULL array argument");
+    if (out_dump && dump_templates <= 0) return fail(err, -2, "dump_templates must be > 0 with out_dump");
+    if (const char* why = scoring_refusal(*p, true)) return fail(err, -2, "%s", why);
+    hipStream_t st;
+    int rc;
+    if ((rc = select_device(err, ctx, st))) return rc;
+    State& s = *g_states.state_of(ctx);
+    // (the table is checked whether or not there are reads; a NULL sequence in any ladder before the limits of the first)
+    if ((rc = set_ladders(err, s, st, Table{n_ladders, prefix, repeat, suffix, max_units}, TREDGPU_MAX_LONG_TEMPLATE_LEN, true)))
+        return rc;
     if (n_reads == 0) return 0;
-    // reads by row class (up to 512 / 1024 / 2048 bp)
-    std::vector<int2> lists[3];
-    for (int64_t r = 0; r < n_reads; ++r) {
+    const size_t n = (size_t)n_reads;
+    for (size_t r = 0; r < n; ++r) {
         const int L = read_len[r];
         if (L < 0 || L > TREDGPU_MAX_LONG_READ_LEN)
-            return fail(g_long_error, -5, "read of %d bp exceeds TREDGPU_MAX_LONG_READ_LEN=%d", L, TREDGPU_MAX_LONG_READ_LEN);
-        if (read_ladder[r] < 0 || read_ladder[r] >= n_ladders) return fail(g_long_error, -2, "read %lld: ladder %d not given", (long long)r, read_ladder[r]);
+            return fail(err, -5, "read of %d bp exceeds TREDGPU_MAX_LONG_READ_LEN=%d", L, TREDGPU_MAX_LONG_READ_LEN);
+        if (read_ladder[r] < 0 || read_ladder[r] >= n_ladders) return fail(err, -2, "read %lld: ladder %d not given", (long long)r, read_ladder[r]);
         if (read_off[r + 1] - read_off[r] != ((L + 15) >> 4) + ((L + 31) >> 5))
-            return fail(g_long_error, -2, "read %lld: read_off does not match read_len (tredgpu_pack_reads layout)", (long long)r);
-        lists[L <= 512 ? 0 : (L <= 1024 ? 1 : 2)].push_back(make_int2((int)r, read_ladder[r]));
+            return fail(err, -2, "read %lld: read_off does not match read_len (tredgpu_pack_reads layout)", (long long)r);
     }
-    hipStream_t st = (hipStream_t)tredgpu_get_stream(ctx);
-    int dev = 0;
-    LCHK(hipStreamGetDevice(st, &dev));
-    LCHK(hipSetDevice(dev));
-    DevBufs b;
-    uint32_t* d_packed; int64_t* d_off; int32_t* d_len; LongLadder* d_lad; uint32_t* d_seq; int2* d_list; int32_t* d_cnt;
-    uint8_t* d_tag; int16_t *d_h, *d_score, *d_dump = nullptr;
-    const size_t words = (size_t)read_off[n_reads], dump_n = out_dump ? (size_t)n_reads * dump_templates * 6 : 0;
-    const size_t n_list = lists[0].size() + lists[1].size() + lists[2].size();
-    LCHK(b.get(&d_packed, words));
-    LCHK(b.get(&d_off, (size_t)n_reads + 1));
-    LCHK(b.get(&d_len, (size_t)n_reads));
-    LCHK(b.get(&d_lad, lad.size()));
-    LCHK(b.get(&d_seq, seq.size()));
-    LCHK(b.get(&d_list, n_list));
-    LCHK(b.get(&d_cnt, 3));
-    LCHK(b.get(&d_tag, (size_t)n_reads));
-    LCHK(b.get(&d_h, (size_t)n_reads));
-    LCHK(b.get(&d_score, (size_t)n_reads));
-    if (out_dump) LCHK(b.get(&d_dump, dump_n));
-    std::vector<int2> all;
-    int32_t cnt[3];
-    for (int k = 0; k < 3; ++k) { cnt[k] = (int32_t)lists[k].size(); all.insert(all.end(), lists[k].begin(), lists[k].end()); }
-    LCHK(hipMemcpyAsync(d_packed, packed, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    LCHK(hipMemcpyAsync(d_off, read_off, ((size_t)n_reads + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    LCHK(hipMemcpyAsync(d_len, read_len, (size_t)n_reads * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    LCHK(hipMemcpyAsync(d_lad, lad.data(), lad.size() * sizeof(LongLadder), hipMemcpyHostToDevice, st));
-    LCHK(hipMemcpyAsync(d_seq, seq.data(), seq.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    LCHK(hipMemcpyAsync(d_list, all.data(), n_list * sizeof(int2), hipMemcpyHostToDevice, st));
-    LCHK(hipMemcpyAsync(d_cnt, cnt, sizeof cnt, hipMemcpyHostToDevice, st));
-    if (out_dump) LCHK(hipMemsetAsync(d_dump, 0xFF, dump_n * sizeof(int16_t), st));
-    SwArgs a;
-    memset(&a, 0, sizeof a);
-    a.packed = d_packed;
-    a.read_off = d_off;
-    a.read_len = d_len;
-    a.seqw = d_seq;
-    a.out_tag = d_tag;
-    a.out_h = d_h;
-    a.out_score = d_score;
-    a.out_dump = d_dump;
+    if ((rc = reads_refusal(err, read_off, read_len, n, -1))) return rc;
+    // reads by row class (up to 512 / 1024 / 2048 bp)
+    std::vector<int32_t> list;
+    std::vector<int64_t> first;
+    bucket_order(n, 3, [&](size_t r) { return read_len[r] <= 512 ? 0 : (read_len[r] <= 1024 ? 1 : 2); }, list, first);
+
+    LongArgs a{};
+    fill_table(a, s, *p);
+    a.flank = p->flank; a.clip = p->clip;
     a.dump_templates = dump_templates;
-    a.p = *p;
+    const size_t dump_n = out_dump ? n * dump_templates * 6 : 0;
+    const int32_t* d_list = nullptr;
+    std::vector<Array> arrays = {
+        arr_in(a.packed, packed, (size_t)read_off[n]), arr_in(a.read_off, read_off, n + 1), arr_in(a.read_len, read_len, n),
+        arr_in(a.read_ladder, read_ladder, n), arr_in(d_list, list.data(), n), arr_out(a.out_tag, out_tag, n), arr_out(a.out_h, out_h, n),
+        arr_out(a.out_score, out_score, n)};
+    if (out_dump) arrays.push_back(arr_out(a.out_dump, out_dump, dump_n));       // (without it a.out_dump stays null)
+    if ((rc = stage(err, s, st, arrays))) return rc;
+    if (out_dump) SIDE_UNIT_CHK(err, hipMemsetAsync(a.out_dump, 0xFF, dump_n * sizeof(int16_t), st));
     // one wavefront per workgroup; each loops over its class's list
-    const int2* at = d_list;
-    if (cnt[0]) sw_long_kernel<8><<<(unsigned)std::min(cnt[0], 2048), 64, 0, st>>>(a, d_lad, at, d_cnt);
-    at += cnt[0];
-    if (cnt[1]) sw_long_kernel<16><<<(unsigned)std::min(cnt[1], 2048), 64, 0, st>>>(a, d_lad, at, d_cnt + 1);
-    at += cnt[1];
-    if (cnt[2]) sw_long_kernel<32><<<(unsigned)std::min(cnt[2], 2048), 64, 0, st>>>(a, d_lad, at, d_cnt + 2);
-    LCHK(hipGetLastError());
-    LCHK(hipMemcpyAsync(out_tag, d_tag, (size_t)n_reads, hipMemcpyDeviceToHost, st));
-    LCHK(hipMemcpyAsync(out_h, d_h, (size_t)n_reads * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-    LCHK(hipMemcpyAsync(out_score, d_score, (size_t)n_reads * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-    if (out_dump) LCHK(hipMemcpyAsync(out_dump, d_dump, dump_n * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-    LCHK(hipStreamSynchronize(st));
-    return 0;
+    auto launch = [&](int c, auto kernel) {
+        a.list = d_list + first[c];
+        a.n_list = (int32_t)(first[c + 1] - first[c]);
+        if (a.n_list) hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(a.n_list, 2048)), dim3(64), 0, st, a);
+    };
+    launch(0, sw_long_kernel<8>);
+    launch(1, sw_long_kernel<16>);
+    launch(2, sw_long_kernel<32>);
+    SIDE_UNIT_CHK(err, hipGetLastError());
+    return read_back(err, s, st, arrays);                          // (list is read by its copy until the stream is drained)
 }
 
 }  // extern "C"

@@ -26,12 +26,12 @@
 //   * after the sweep score1 / ref_end1 are the wave-wide arg-max of colw[c] << 16 | (0xFFFF - c) (the first column that
 //     reaches the maximum), rule 2 picks the array and rule 3 is the same arg-max over the allowed columns.
 //   * nothing is written to global memory but the item's four values and its status.
-#include "cigar_unit.h"
+#include "side_unit.h"
 #include "../../include/tredlong.h"
 #include "../../include/tredsecond.h"
 
 namespace {
-using namespace cigar_unit;
+using namespace side_unit;
 
 thread_local std::string g_second_error;   // the text of tredsecond_last_error()
 
@@ -65,16 +65,6 @@ __device__ __forceinline__ int wave_max(int x) {
     return x;
 }
 
-// 5-bit fields, field k = 16 + score of read code k (0..3, 4 = N or a padding row) against template letter `let`
-__device__ __forceinline__ uint32_t score_lut(int let, int match, int mismatch) {
-    uint32_t lut = 0;
-    for (int k = 0; k < 5; ++k) {
-        const int s = (k == 4 || let > 3) ? 0 : k == let ? match : -mismatch;   // N on either side scores 0
-        lut |= (uint32_t)(s + 16) << (5 * k);
-    }
-    return lut;
-}
-
 // One DP column for this lane's R rows; returns through mw / mb the lane's maxima over its first nw / nb rows, as plain
 // scores (0 where it has no such row).
 template <int R>
@@ -99,14 +89,7 @@ __device__ __forceinline__ void second_column(const uint32_t (&code)[(R + 3) / 4
         E[r] = max(E[r], q);                                    // E of the next column
     }
     // exclusive max scan over the 64 lanes: F entering this lane from the rows above it
-    int x = run;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, (unsigned)d, 64);
-        if (lane >= d) x = max(x, y);
-    }
-    int F = __shfl_up(x, 1u, 64);
-    if (lane == 0) F = SNEG;
+    int F = wave_excl_max(run, lane, SNEG);
     int m8 = SNEG, w = SNEG, b = SNEG;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -129,15 +112,11 @@ template <int R>
 __device__ int second_item(const SecondArgs& a, int64_t item, uint16_t* colw, uint16_t* colb, int (&res)[4]) {
     const int lane = threadIdx.x;
     const int lad = a.item_ladder[item], tpl = a.item_template[item], L = a.read_len[item];
-    if (lad < 0 || lad >= a.n_ladders || L < 0) return TREDGPU_SECOND_BAD_ITEM;
-    const LadderRecord& d = a.ladders[lad];                          // (read in place: a copy indexed by strand is scratch)
-    const int max_units = d.max_units;
-    if (tpl < 0 || tpl >= (max_units > 0 ? 2 * max_units : 1)) return TREDGPU_SECOND_BAD_ITEM;
-    const int strand = max_units > 0 ? (tpl & 1) : 0;
-    const int trunk = d.alen[strand] + (max_units > 0 ? d.period * (tpl / 2 + 1) : 0);
-    const int tlen = trunk + d.blen[strand];
+    Template t;
+    if (!template_of(a, lad, tpl, t) || L < 0) return TREDGPU_SECOND_BAD_ITEM;
+    const int trunk = t.trunk, tlen = t.tlen;
     if (L > TREDGPU_MAX_LONG_READ_LEN || L > 64 * R || tlen > TREDGPU_MAX_LONG_TEMPLATE_LEN) return TREDGPU_SECOND_TOO_LONG;
-    const uint8_t *tr = a.letters + d.trunk_off[strand], *br = a.letters + d.branch_off[strand];
+    const uint8_t *tr = t.tr, *br = t.br;
     const uint32_t* rec = a.packed + a.read_off[item];
     const int nb_words = (L + 15) >> 4;
     const int ge = a.gap_extend, c0 = a.gap_open - a.gap_extend;
@@ -228,7 +207,7 @@ __global__ __launch_bounds__(64) void second_kernel(SecondArgs a) {
     }
 }
 
-struct State : StateBase {};   // st: the six inputs, the two outputs, the class lists
+struct State : StateBase {};
 Registry<State> g_states;
 
 }  // namespace
@@ -253,40 +232,29 @@ int tredsecond_sw_second(tredgpu_ctx* ctx, int32_t n_ladders, const char* const*
     if ((rc = set_ladders(err, s, st, t, 0))) return rc;           // (a template beyond the limit is the item's TOO_LONG)
 
     // the items by row class; one the kernel refuses by its read's length goes to the first
-    std::vector<int32_t> list(n);
-    int32_t cnt[N_CLASSES] = {}, first[N_CLASSES];
-    auto class_of = [](int L) {
+    std::vector<int32_t> list;
+    std::vector<int64_t> first;
+    bucket_order(n, N_CLASSES, [&](size_t k) {
+        const int L = read_len[k];
         int c = 0;
         while (c < N_CLASSES - 1 && L > (64 << c)) ++c;
         return L < 0 || L > TREDGPU_MAX_LONG_READ_LEN ? 0 : c;
-    };
-    for (size_t k = 0; k < n; ++k) cnt[class_of(read_len[k])] += 1;
-    for (int c = 0, at = 0; c < N_CLASSES; at += cnt[c++]) first[c] = at;
-    {
-        int32_t fill[N_CLASSES];
-        std::copy(first, first + N_CLASSES, fill);
-        for (size_t k = 0; k < n; ++k) list[fill[class_of(read_len[k])]++] = (int32_t)k;
-    }
+    }, list, first);
 
-    const size_t sizes[9] = {(size_t)read_off[n] * 4, (n + 1) * 8, n * 4, n * 4, n * 4, n * 4, n * 16, n * 4, n * 4};
-    const void* src[9] = {packed, read_off, read_len, item_ladder, item_template, mask_len, nullptr, nullptr, list.data()};
-    for (int k = 0; k < 9; ++k)
-        if ((rc = ensure(err, s.st[k], sizes[k], st))) return rc;
-    for (int k = 0; k < 9; ++k)
-        if (src[k] && sizes[k]) CIGAR_UNIT_CHK(err, hipMemcpyAsync(s.st[k].p, src[k], sizes[k], hipMemcpyHostToDevice, st));
     SecondArgs a{};
-    a.packed = (const uint32_t*)s.st[0].p; a.read_off = (const int64_t*)s.st[1].p; a.read_len = (const int32_t*)s.st[2].p;
-    a.item_ladder = (const int32_t*)s.st[3].p; a.item_template = (const int32_t*)s.st[4].p; a.mask_len = (const int32_t*)s.st[5].p;
-    a.out = (int32_t*)s.st[6].p; a.out_status = (int32_t*)s.st[7].p;
-    a.ladders = (const LadderRecord*)s.ladders.p; a.letters = (const uint8_t*)s.letters.p; a.n_ladders = s.n_ladders;
-    a.match = p->match; a.mismatch = p->mismatch; a.gap_open = p->gap_open; a.gap_extend = p->gap_extend;
+    fill_table(a, s, *p);
+    const int32_t* d_list = nullptr;
+    const std::vector<Array> arrays = {
+        arr_in(a.packed, packed, (size_t)read_off[n]), arr_in(a.read_off, read_off, n + 1), arr_in(a.read_len, read_len, n),
+        arr_in(a.item_ladder, item_ladder, n), arr_in(a.item_template, item_template, n), arr_in(a.mask_len, mask_len, n),
+        arr_in(d_list, list.data(), n), arr_out(a.out, out, n * 4), arr_out(a.out_status, out_status, n)};
+    if ((rc = stage(err, s, st, arrays))) return rc;
 
     if ((rc = timed_begin(err, s, st))) return rc;
     auto launch = [&](int c, auto kernel) {
-        if (!cnt[c]) return;
-        a.list = (const int32_t*)s.st[8].p + first[c];
-        a.n_list = cnt[c];
-        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(cnt[c], MAX_WAVES)), dim3(64), 0, st, a);
+        a.list = d_list + first[c];
+        a.n_list = (int32_t)(first[c + 1] - first[c]);
+        if (a.n_list) hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(a.n_list, MAX_WAVES)), dim3(64), 0, st, a);
     };
     launch(0, second_kernel<1>);
     launch(1, second_kernel<2>);
@@ -295,10 +263,7 @@ int tredsecond_sw_second(tredgpu_ctx* ctx, int32_t n_ladders, const char* const*
     launch(4, second_kernel<16>);
     launch(5, second_kernel<32>);
     if ((rc = timed_end(err, s, st))) return rc;
-    CIGAR_UNIT_CHK(err, hipMemcpyAsync(out, a.out, n * 16, hipMemcpyDeviceToHost, st));
-    CIGAR_UNIT_CHK(err, hipMemcpyAsync(out_status, a.out_status, n * 4, hipMemcpyDeviceToHost, st));
-    CIGAR_UNIT_CHK(err, hipStreamSynchronize(st));                 // (list is read by the copy above until here)
-    return 0;
+    return read_back(err, s, st, arrays);                          // (list is read by its copy until the stream is drained)
 }
 
 int tredsecond_get_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms) { return timing(g_second_error, g_states, ctx, launches, total_ms, false); }
