@@ -19,10 +19,8 @@ from collections.abc import Sequence
 import numpy as np
 
 from . import _lib, bamio
+from .bamio import DNAPE_ELONGATE, FLANKMATCH, SPAN    # the loci's geometry: the defaults of bamio's scan and plans
 
-SPAN = 1000                 # half width of the fetch window around the tract, and the pair-length cap
-FLANKMATCH = 9              # bases of flank an alignment must reach to count as anchored
-DNAPE_ELONGATE = 10 * SPAN  # pairs are collected this far on either side of the tract
 MAX_READ_LEN = 480          # longest read the SW kernel holds (include/tredgpu.h)
 MAX_TEMPLATE_LEN = 511      # longest template (prefix + repeat * max_units + suffix)
 MAX_LONG_READ_LEN = 2048    # the same with the long-read path on (scan_sample(long_reads=True))
@@ -157,6 +155,25 @@ def walk_need(coffset, host, results, alt_need=None):
     return need
 
 
+# ---- what the host's scan and the device's selection must agree on, beside the library's own geometry ------------------
+def window_widths(loci):
+    """Per locus the bases its depth sum is divided by: the window [repeat_start - SPAN, from 0 on; repeat_end + SPAN] with
+    both ends counted (BamDepth.region_depth, bam_parser.py:404-411)."""
+    return np.array([t.repeat_end + SPAN - max(0, t.repeat_start - SPAN) + 1 for t in loci], np.float64)
+
+
+def selection_range(sites, readlen):
+    """(pos_lo, pos_hi) per site of a SITE_DTYPE array: a selected read starts within one read length of the tract
+    (bam_parser.py:209-213), as the library's scan takes it."""
+    return (np.maximum(sites["repeat_start"].astype(np.int64) - readlen, 0), sites["repeat_end"].astype(np.int64) + readlen)
+
+
+def ladder_fits(t, readlen, max_template=MAX_TEMPLATE_LEN):
+    """Whether the locus' longest template at this read length (prefix + repeat * max_units + suffix) fits the kernel's
+    columns."""
+    return len(t.prefix) + t.period * -(-readlen // t.period) + len(t.suffix) <= max_template
+
+
 def scan_sample(path, repo, names, clip=False, alts=True, readlen=None, want_sex=None, handle=None, pe=None, alt=None,
                 long_reads=False):
     """Read one sample: sex and read length, then depth / reads / pair lengths of every locus in `names`.
@@ -191,14 +208,12 @@ def scan_sample(path, repo, names, clip=False, alts=True, readlen=None, want_sex
         except Exception:
             pass
     sites, regions = _site_arrays(repo, s.names, s.loci, f)
-    s.unit, pools = f.scan(sites, regions, s.readlen, pad=SPAN, flank=FLANKMATCH, pe_reach=DNAPE_ELONGATE, span=SPAN,
-                           use_alts=alts and not clip, **({"pe": pe, "alt": alt} if pe is not None else {}))
+    s.unit, pools = f.scan(sites, regions, s.readlen, use_alts=alts and not clip, **({"pe": pe, "alt": alt} if pe is not None else {}))
     s.packed, s.word_off, s.read_len = pools["packed"], pools["word_off"], pools["read_len"]
     s.seq4, s.seq4_off = pools["seq4"], pools["seq4_off"]
     s.name_blob, s.name_off, s.name_id = pools["names"], pools["name_off"], pools["name_id"]
     s.global_lens, s.target_lens = pools["global_lens"], pools["target_lens"]
-    window = np.array([t.repeat_end + SPAN - max(0, t.repeat_start - SPAN) + 1 for t in s.loci], np.float64)
-    s.depth = np.where(s.unit["depth_status"] == 0, s.unit["depth_sum"] / window, 30.0)
+    s.depth = np.where(s.unit["depth_status"] == 0, s.unit["depth_sum"] / window_widths(s.loci), 30.0)
     s.ploidy = np.array([1 if (s.gender == "Male" and t.is_xlinked) else t.ploidy for t in s.loci], np.int32)
     admit(s)
     if handle is None:
@@ -231,7 +246,7 @@ def admit(s):
             why = "a paired read without an alignment end (pair-length extraction)"
         elif longest > max_read:
             why = "a {} bp read: the SW kernel holds reads up to {} bp".format(longest, max_read)
-        elif len(t.prefix) + t.period * -(-s.readlen // t.period) + len(t.suffix) > max_template:
+        elif not ladder_fits(t, s.readlen, max_template):
             why = "template ladder longer than {} columns".format(max_template)
         if why:
             _log.error("Exception on `%s` %s (%s)", s.path, t.name, why)

@@ -857,6 +857,19 @@ class ScanOpts(C.Structure):
                                          "want_pe")]
 
 
+# A locus' geometry under the reference's names (bam_parser.py:26-29), defined here once: the defaults of scan / plan /
+# plan_walks / plan_alt_walks (pad = span = SPAN, flank = FLANKMATCH, pe_reach = DNAPE_ELONGATE), and what bam_parser uses.
+SPAN = 1000                 # half width of the fetch window around the tract, and the pair-length cap
+FLANKMATCH = 9              # bases of flank an alignment must reach to count as anchored
+DNAPE_ELONGATE = 10 * SPAN  # pairs are collected this far on either side of the tract
+
+
+def _scan_opts(readlen, pad, flank, pe_reach, span, use_alts=False, want_depth=True, want_pe=True):
+    """The tredbam_scan_opts of one call."""
+    return ScanOpts(int(readlen), int(pad), int(flank), int(pe_reach), int(span), int(bool(use_alts)), int(bool(want_depth)),
+                    int(bool(want_pe)))
+
+
 class Pools(C.Structure):
     _fields_ = [("n_reads", C.c_int64), ("n_words", C.c_int64), ("n_global", C.c_int64), ("n_target", C.c_int64),
                 ("packed", C.c_void_p), ("word_off", C.c_void_p), ("read_len", C.c_void_p), ("seq4", C.c_void_p),
@@ -1025,7 +1038,28 @@ class NativeAlignmentFile(object):
     def tid(self, chrom):
         return self._tid.get(chrom, -1)
 
-    def scan(self, sites, alts, readlen, pad=1000, flank=9, pe_reach=10000, span=1000, use_alts=True,
+    def _regions(self, regions):
+        """[(contig, start, end)] -> REGION_DTYPE (never empty: its address is handed in); an unknown contig gets tid -1."""
+        rg = np.zeros(max(len(regions), 1), REGION_DTYPE)
+        for k, (contig, lo, hi) in enumerate(regions):
+            rg[k] = (self._tid.get(contig, -1), lo, hi)
+        return rg
+
+    def _plan_walks(self, planner, n_tasks, cap, *args):
+        """One of the library's walk planners: planner(handle, *args, tasks, chunks, cap), called again with four times the
+        room while it returns -3 -> (the first n_tasks tasks, the chunks written)."""
+        tasks = np.zeros(max(n_tasks, 1), WALK_TASK_DTYPE)
+        while True:
+            chunks = np.zeros(cap, WALK_CHUNK_DTYPE)
+            n = planner(self._h, *args, tasks.ctypes.data, chunks.ctypes.data, cap)
+            if n == -3:
+                cap *= 4
+                continue
+            if n < 0:
+                raise ValueError(self._err())
+            return tasks[:n_tasks], chunks[:n]
+
+    def scan(self, sites, alts, readlen, pad=SPAN, flank=FLANKMATCH, pe_reach=DNAPE_ELONGATE, span=SPAN, use_alts=True,
              want_depth=True, want_pe=True, pe=None, alt=None):
         """tredbam_scan: `sites` (SITE_DTYPE) and `alts` (REGION_DTYPE) -> (units SCAN_UNIT_DTYPE, dict of pool
         arrays).  One native call; the GIL is released while it runs.  pe = (results WALK_RESULT_DTYPE per site, global
@@ -1034,8 +1068,7 @@ class NativeAlignmentFile(object):
         sites = np.ascontiguousarray(sites, SITE_DTYPE)
         alts = np.ascontiguousarray(alts if len(alts) else np.zeros(1, REGION_DTYPE), REGION_DTYPE)
         units = np.zeros(len(sites), SCAN_UNIT_DTYPE)
-        o = ScanOpts(int(readlen), int(pad), int(flank), int(pe_reach), int(span), int(bool(use_alts)),
-                     int(bool(want_depth)), int(bool(want_pe)))
+        o = _scan_opts(readlen, pad, flank, pe_reach, span, use_alts, want_depth, want_pe)
         if pe is not None:
             res = np.ascontiguousarray(pe[0], WALK_RESULT_DTYPE)
             gp = np.ascontiguousarray(pe[1] if len(pe[1]) else np.zeros(1, np.int32), np.int32)
@@ -1076,79 +1109,42 @@ class NativeAlignmentFile(object):
         return units, pools
 
     # ---- blocks inflated elsewhere (the GPU's batch decoder, _lib.Inflater) ----
-    def plan(self, sites, alts, readlen, pad=1000, flank=9, pe_reach=10000, span=1000, use_alts=True, want_depth=True,
+    def plan(self, sites, alts, readlen, pad=SPAN, flank=FLANKMATCH, pe_reach=DNAPE_ELONGATE, span=SPAN, use_alts=True, want_depth=True,
              want_pe=True, extra=()):
         """tredbam_plan: the BGZF blocks scan(...) with the same arguments will read -> (n_blocks, bytes their payloads
         take in a staging buffer, bytes they inflate to).  extra: (contig, start, end) of other queries to cover."""
         sites = np.ascontiguousarray(sites, SITE_DTYPE)
         alts = np.ascontiguousarray(alts if len(alts) else np.zeros(1, REGION_DTYPE), REGION_DTYPE)
-        o = ScanOpts(int(readlen), int(pad), int(flank), int(pe_reach), int(span), int(bool(use_alts)),
-                     int(bool(want_depth)), int(bool(want_pe)))
-        cb, ob = C.c_int64(), C.c_int64()
-        ex = np.zeros(max(len(extra), 1), REGION_DTYPE)
-        for k, (contig, lo, hi) in enumerate(extra):
-            ex[k] = (self._tid.get(contig, -1), lo, hi)
+        o = _scan_opts(readlen, pad, flank, pe_reach, span, use_alts, want_depth, want_pe)
+        cb, ob, ex = C.c_int64(), C.c_int64(), self._regions(extra)
         n = self._lib.tredbam_plan(self._h, sites.ctypes.data, len(sites), alts.ctypes.data, C.byref(o), ex.ctypes.data, len(extra),
                                    C.byref(cb), C.byref(ob))
         if n < 0:
             raise ValueError(self._err())
         return int(n), cb.value, ob.value
 
-    def plan_walks(self, sites, readlen, pad=1000, flank=9, pe_reach=10000, span=1000):
+    def plan_walks(self, sites, readlen, pad=SPAN, flank=FLANKMATCH, pe_reach=DNAPE_ELONGATE, span=SPAN):
         """tredbam_plan_walks (after plan() with the same arguments): (tasks WALK_TASK_DTYPE per site, chunks
         WALK_CHUNK_DTYPE) of the pair-length walks, for tredgpu's inflate_walk."""
         sites = np.ascontiguousarray(sites, SITE_DTYPE)
-        o = ScanOpts(int(readlen), int(pad), int(flank), int(pe_reach), int(span), 0, 1, 1)
-        tasks = np.zeros(len(sites), WALK_TASK_DTYPE)
-        cap = 8 * len(sites) + 16
-        while True:
-            chunks = np.zeros(cap, WALK_CHUNK_DTYPE)
-            n = self._lib.tredbam_plan_walks(self._h, sites.ctypes.data, len(sites), C.byref(o), tasks.ctypes.data,
-                                             chunks.ctypes.data, cap)
-            if n == -3:
-                cap *= 4
-                continue
-            if n < 0:
-                raise ValueError(self._err())
-            return tasks, chunks[:n]
+        o = _scan_opts(readlen, pad, flank, pe_reach, span)
+        return self._plan_walks(self._lib.tredbam_plan_walks, len(sites), 8 * len(sites) + 16, sites.ctypes.data, len(sites), C.byref(o))
 
-    def plan_alt_walks(self, sites, alts, readlen, pad=1000, flank=9, pe_reach=10000, span=1000, use_alts=True):
+    def plan_alt_walks(self, sites, alts, readlen, pad=SPAN, flank=FLANKMATCH, pe_reach=DNAPE_ELONGATE, span=SPAN, use_alts=True):
         """tredbam_plan_alt_walks (after plan()): (tasks WALK_TASK_DTYPE, one per entry of `alts`; chunks) of the walks over
         the alternative loci."""
         sites = np.ascontiguousarray(sites, SITE_DTYPE)
         n_alts = len(alts)
         alts = np.ascontiguousarray(alts if n_alts else np.zeros(1, REGION_DTYPE), REGION_DTYPE)
-        o = ScanOpts(int(readlen), int(pad), int(flank), int(pe_reach), int(span), int(bool(use_alts)), 1, 1)
-        tasks = np.zeros(max(n_alts, 1), WALK_TASK_DTYPE)
-        cap = 4 * n_alts + 16
-        while True:
-            chunks = np.zeros(cap, WALK_CHUNK_DTYPE)
-            n = self._lib.tredbam_plan_alt_walks(self._h, sites.ctypes.data, len(sites), alts.ctypes.data, n_alts, C.byref(o),
-                                                 tasks.ctypes.data, chunks.ctypes.data, cap)
-            if n == -3:
-                cap *= 4
-                continue
-            if n < 0:
-                raise ValueError(self._err())
-            return tasks[:n_alts], chunks[:n]
+        o = _scan_opts(readlen, pad, flank, pe_reach, span, use_alts)
+        return self._plan_walks(self._lib.tredbam_plan_alt_walks, n_alts, 4 * n_alts + 16, sites.ctypes.data, len(sites),
+                                alts.ctypes.data, n_alts, C.byref(o))
 
     def plan_region_walks(self, regions):
         """tredbam_plan_region_walks (after plan() with the regions among its `extra`): (tasks WALK_TASK_DTYPE, chunks) of plain
         region walks -- regions: [(contig, start, end)]; a task's window is its region and it forms no pairs (span 0)."""
-        rg = np.zeros(max(len(regions), 1), REGION_DTYPE)
-        for k, (contig, lo, hi) in enumerate(regions):
-            rg[k] = (self._tid.get(contig, -1), lo, hi)
-        tasks = np.zeros(max(len(regions), 1), WALK_TASK_DTYPE)
-        cap = 8 * len(regions) + 16
-        while True:
-            chunks = np.zeros(cap, WALK_CHUNK_DTYPE)
-            n = self._lib.tredbam_plan_region_walks(self._h, rg.ctypes.data, len(regions), tasks.ctypes.data, chunks.ctypes.data, cap)
-            if n == -3:
-                cap *= 4
-                continue
-            if n < 0:
-                raise ValueError(self._err())
-            return tasks[:len(regions)], chunks[:n]
+        rg = self._regions(regions)
+        return self._plan_walks(self._lib.tredbam_plan_region_walks, len(regions), 8 * len(regions) + 16, rg.ctypes.data, len(regions))
 
     def plan_blocks(self):
         """tredbam_plan_blocks: (compressed offset, compressed length, trailer CRC-32, read-by-the-scan-itself flag) of

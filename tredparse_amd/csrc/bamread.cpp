@@ -11,8 +11,6 @@
 #include <zlib.h>
 
 #include <algorithm>
-#include <charconv>
-#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -106,9 +104,12 @@ struct tredbam {
     struct Planned { int64_t coffset, payload_off; int32_t payload_len; int64_t clen; uint32_t crc, isize; uint8_t host; };
     struct Preloaded { const uint8_t* data; uint32_t size; int64_t clen; uint32_t crc; bool checked; };
     std::vector<Planned> plan;
+    std::unordered_map<int64_t, int32_t> plan_index;   // compressed offset -> place in `plan`; filled and cleared with it
     std::unordered_map<int64_t, Preloaded> preloaded;
     int64_t preload_hits = 0, preload_misses = 0;
-    int64_t pe_pool_global = -1, pe_pool_target = -1;   // lengths of the pools tredbam_scan_pe / _walked index (tredbam_pe_pool_sizes)
+    // lengths of the pools tredbam_scan_pe / _walked index (tredbam_pe_pool_sizes).  A wart: an argument of those two calls
+    // kept on the handle between calls, because their signatures have no room for it; it goes with the next ABI change
+    int64_t pe_pool_global = -1, pe_pool_target = -1;
     tredbam_inflate::Tables inflate_tables;        // decoding tables of the block decoder (inflate_block.h)
     // header
     std::vector<std::string> ref_names;
@@ -866,6 +867,56 @@ void pool_read(tredbam* b, const uint8_t* r, std::unordered_map<std::string, int
     b->sc_name_id.push_back(it->second);
 }
 
+// The coordinates of one locus (tredbam_scan_opts in include/tredbam.h), in the one place the scan, the plan and the walk
+// tasks take them from -- the device's selection follows the tasks, the host's scan this struct, and they must agree.
+struct SiteGeometry {
+    int64_t win_lo, win_hi;   // repeat +- pad, from 0 on: the window of the depth and of the read selection
+    int64_t pos_lo, pos_hi;   // repeat +- readlen, from 0 on: where a selected read starts
+    int64_t pe_lo, pe_hi;     // repeat +- pe_reach, from 0 on: the region the pair lengths are taken from
+    int64_t t_lo, t_hi;       // repeat +- flank: a pair that reaches beyond both is a target pair
+};
+SiteGeometry site_geometry(const tredbam_site& st, const tredbam_scan_opts& o) {
+    const int64_t lo = st.repeat_start, hi = st.repeat_end;
+    SiteGeometry g;
+    g.win_lo = std::max<int64_t>(0, lo - o.pad);       g.win_hi = hi + o.pad;
+    g.pos_lo = std::max<int64_t>(0, lo - o.readlen);   g.pos_hi = hi + o.readlen;
+    g.pe_lo = std::max<int64_t>(0, lo - o.pe_reach);   g.pe_hi = hi + o.pe_reach;
+    g.t_lo = lo - o.flank;                             g.t_hi = hi + o.flank;
+    return g;
+}
+
+// The chunk array of one planner call, how far it is filled, and the merged index chunks of the region at hand.
+struct WalkChunks {
+    tredbam_walk_chunk* chunks;
+    int64_t n, cap;
+    std::vector<std::pair<uint64_t, uint64_t>> merged;
+};
+enum WalkPlan { NOT_WALKABLE, WALKABLE, NO_ROOM };
+
+// The walk over [start, end) of contig tid as task t, shared by the three planners: chunk_first and block_end are set in
+// any case and n_chunks stays -1 until the region is proven walkable (its contig is in the file, the index answers, its
+// end fits 32 bits) -- asked first, so that only chunks that would be written can find no room (NO_ROOM: the caller returns
+// -3).  Then start / end as the query clamps them, and the merged index chunks appended as (planned block, offset in it) ->
+// end virtual offset; begin_block -1: a block the plan does not hold (every one before any tredbam_plan).
+WalkPlan plan_task(tredbam* b, int32_t tid, int64_t start, int64_t end, tredbam_walk_task& t, WalkChunks& out) {
+    t.chunk_first = (int32_t)out.n;
+    t.n_chunks = -1;
+    t.block_end = (int32_t)b->plan.size();
+    if (tid < 0 || region_chunks(b, tid, start, end, out.merged) != 0 || end > INT32_MAX) return NOT_WALKABLE;
+    if ((int64_t)out.merged.size() > out.cap - out.n) return NO_ROOM;
+    t.start = (int32_t)start;
+    t.end = (int32_t)end;
+    for (const auto& ch : out.merged) {
+        tredbam_walk_chunk& c = out.chunks[out.n++];
+        const auto at = b->plan_index.find((int64_t)(ch.first >> 16));
+        c.begin_block = at == b->plan_index.end() ? -1 : at->second;
+        c.begin_upos = (int32_t)(ch.first & 0xFFFF);
+        c.end_voffset = ch.second;
+    }
+    t.n_chunks = (int32_t)out.merged.size();
+    return WALKABLE;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1031,222 +1082,6 @@ uint32_t tredbam_crc32(uint32_t crc, const uint8_t* buf, int64_t len) {
     return (buf && len > 0) ? tredbam_crc::crc32(crc, buf, (size_t)len) : crc;
 }
 
-int64_t tredbam_details_json(const uint8_t* seq4, const int64_t* seq4_off, const int32_t* read_len, const char* names,
-                             const int64_t* name_off, const int64_t* reads, const uint8_t* tags, const int32_t* hs,
-                             int64_t n, char* out, int64_t cap) {
-    if (n < 0 || !out || cap < 2 || (n > 0 && (!seq4 || !seq4_off || !read_len || !names || !name_off || !reads || !tags || !hs)))
-        return -2;
-    static const char* const TAGS[6] = {nullptr, "FULL", "PREF", "POST", "REPT", "HANG"};
-    static const char BASES[] = "=ACMGRSVTWYHKDBN";
-    char* p = out;
-    char* const end = out + cap;
-    auto put = [&](const char* s, size_t len) { memcpy(p, s, len); p += len; };
-#define TREDBAM_LIT(S) put(S, sizeof(S) - 1)
-    if (n == 0) { TREDBAM_LIT("[]"); return p - out; }
-    TREDBAM_LIT("[\n");
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t rd = reads[i];
-        const int64_t n0 = name_off[rd], n1 = name_off[rd + 1];
-        const int32_t L = read_len[rd];
-        if (tags[i] < 1 || tags[i] > 5 || L < 0 || n1 < n0) return -2;
-        // worst case of this element: fixed text < 160, the name doubled by escapes, the bases, 11 digits
-        if ((int64_t)(end - p) < 200 + 2 * (n1 - n0) + L) return -3;
-        TREDBAM_LIT("            {\n                \"h\": ");
-        p += snprintf(p, 16, "%d", (int)hs[i]);
-        TREDBAM_LIT(",\n                \"id\": \"");
-        for (int64_t k = n0; k < n1; ++k) {
-            const unsigned char c = (unsigned char)names[k];
-            if (c < 0x20 || c >= 0x7f) return -1;
-            if (c == '"' || c == '\\') *p++ = '\\';
-            *p++ = (char)c;
-        }
-        TREDBAM_LIT("\",\n                \"seq\": \"");
-        const uint8_t* sq = seq4 + seq4_off[rd];
-        {   // two bases per byte of the 4-bit sequence: one table look-up and one 2-byte store per pair
-            static const struct Pairs { char t[256][2]; Pairs() { for (int b = 0; b < 256; ++b) { t[b][0] = BASES[b >> 4]; t[b][1] = BASES[b & 15]; } } } PAIRS;
-            const int32_t whole = L >> 1;
-            for (int32_t k = 0; k < whole; ++k, p += 2) memcpy(p, PAIRS.t[sq[k]], 2);
-            if (L & 1) *p++ = BASES[sq[whole] >> 4];
-        }
-        TREDBAM_LIT("\",\n                \"tag\": \"");
-        put(TAGS[tags[i]], 4);
-        TREDBAM_LIT("\"\n            }");
-        if (i + 1 < n) TREDBAM_LIT(",\n");
-    }
-    if (end - p < 16) return -3;
-    TREDBAM_LIT("\n        ]");
-#undef TREDBAM_LIT
-    return p - out;
-}
-
-// Python's repr(float) (float_repr_style 'short'): the shortest digit string that round-trips -- std::to_chars
-// produces the same digits -- laid out in exponent form when the decimal exponent is <= -5 or >= 16, else positionally
-// with ".0" appended to integers.
-int tredbam_float_repr(double x, char* out) {
-    if (!out || !std::isfinite(x)) return -1;
-    char* p = out;
-    if (std::signbit(x)) { *p++ = '-'; x = -x; }
-    if (x == 0) { memcpy(p, "0.0", 3); return (int)(p - out) + 3; }
-    char sci[40];
-    const auto res = std::to_chars(sci, sci + sizeof sci, x, std::chars_format::scientific);
-    // d[.ddd]e[+-]XX[X]
-    char digits[24];
-    int nd = 0;
-    const char* q = sci;
-    for (; q < res.ptr && *q != 'e'; ++q) if (*q != '.') digits[nd++] = *q;
-    int e10 = 0;
-    {
-        const char* r = q + 1;
-        const bool neg = *r == '-';
-        ++r;
-        for (; r < res.ptr; ++r) e10 = e10 * 10 + (*r - '0');
-        if (neg) e10 = -e10;
-    }
-    if (e10 <= -5 || e10 >= 16) {                      // exponent form: to_chars' own text is Python's
-        const size_t len = (size_t)(res.ptr - sci);
-        memcpy(p, sci, len);
-        return (int)(p - out) + (int)len;
-    }
-    if (e10 >= 0) {
-        for (int i = 0; i <= e10; ++i) *p++ = i < nd ? digits[i] : '0';
-        *p++ = '.';
-        if (nd > e10 + 1) for (int i = e10 + 1; i < nd; ++i) *p++ = digits[i];
-        else *p++ = '0';
-    } else {
-        *p++ = '0'; *p++ = '.';
-        for (int i = 0; i < -e10 - 1; ++i) *p++ = '0';
-        for (int i = 0; i < nd; ++i) *p++ = digits[i];
-    }
-    return (int)(p - out);
-}
-
-namespace {
-inline int key_int(char* out, int32_t v) {                 // decimal text of v (at most 11 bytes), its length
-    char buf[12];
-    char* p = buf + sizeof buf;
-    uint32_t u = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
-    do { *--p = (char)('0' + u % 10); u /= 10; } while (u);
-    if (v < 0) *--p = '-';
-    const int n = (int)(buf + sizeof buf - p);
-    memcpy(out, p, (size_t)n);
-    return n;
-}
-}  // namespace
-
-int64_t tredbam_sparse_json(const int32_t* a, const int32_t* b, const double* values, int64_t n, int32_t depth,
-                            char* out, int64_t cap) {
-    if (n < 0 || depth < 0 || depth > 16 || !out || cap < 2 || (n > 0 && (!a || !values))) return -2;
-    char* p = out;
-    char* const end = out + cap;
-    if (n == 0) { memcpy(p, "{}", 2); return 2; }
-    struct Item { char key[24]; int klen; int64_t at; };
-    std::vector<Item> items((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        Item& it = items[(size_t)i];
-        it.klen = key_int(it.key, a[i]);
-        if (b) { it.key[it.klen++] = ','; it.klen += key_int(it.key + it.klen, b[i]); }
-        it.at = i;
-    }
-    std::sort(items.begin(), items.end(), [](const Item& x, const Item& y) {
-        const int c = memcmp(x.key, y.key, (size_t)std::min(x.klen, y.klen));
-        return c != 0 ? c < 0 : x.klen < y.klen;
-    });
-    for (size_t i = 1; i < items.size(); ++i)
-        if (items[i].klen == items[i - 1].klen && memcmp(items[i].key, items[i - 1].key, (size_t)items[i].klen) == 0) return -1;
-    const int pad = 4 * (depth + 1);
-    *p++ = '{'; *p++ = '\n';
-    for (size_t i = 0; i < items.size(); ++i) {
-        if (end - p < pad + 80) return -3;
-        memset(p, ' ', (size_t)pad); p += pad;
-        *p++ = '"';
-        memcpy(p, items[i].key, (size_t)items[i].klen); p += items[i].klen;
-        *p++ = '"'; *p++ = ':'; *p++ = ' ';
-        const int len = tredbam_float_repr(values[items[i].at], p);
-        if (len < 0) return -1;
-        p += len;
-        if (i + 1 < items.size()) *p++ = ',';
-        *p++ = '\n';
-    }
-    if (end - p < 4 * depth + 2) return -3;
-    memset(p, ' ', (size_t)(4 * depth)); p += 4 * depth;
-    *p++ = '}';
-    return p - out;
-}
-
-// Many distributions / many details lists in one call (a sample's 90 + 30 of them: the per-call cost of the binding
-// was a third of the driver thread's time per sample).  Item k covers entries off[k] .. off[k+1] of the input arrays;
-// its text lands at out[out_off[k] .. out_off[k+1]); status[k] = 0, or the single call's -1 (text left empty: the
-// caller's generic encoder takes that item).  Returns the bytes written, -3 when cap is too small, -2 on bad arguments.
-int64_t tredbam_sparse_json_many(const int32_t* a, const int32_t* b, const double* values, const int64_t* off,
-                                 const uint8_t* two_part, int64_t n_items, int32_t depth, char* out, int64_t cap,
-                                 int64_t* out_off, int8_t* status) {
-    if (n_items < 0 || !off || !two_part || !out || !out_off || !status) return -2;
-    int64_t at = 0;
-    out_off[0] = 0;
-    for (int64_t k = 0; k < n_items; ++k) {
-        const int64_t n = off[k + 1] - off[k];
-        if (n < 0 || (two_part[k] && !b)) return -2;
-        const int64_t got = tredbam_sparse_json(a ? a + off[k] : nullptr, two_part[k] ? b + off[k] : nullptr,
-                                                values ? values + off[k] : nullptr, n, depth, out + at, cap - at);
-        if (got == -3 || got == -2) return got;
-        status[k] = got < 0 ? -1 : 0;
-        if (got > 0) at += got;
-        out_off[k + 1] = at;
-    }
-    return at;
-}
-
-int64_t tredbam_details_json_many(const uint8_t* seq4, const int64_t* seq4_off, const int32_t* read_len, const char* names,
-                                  const int64_t* name_off, const int64_t* reads, const uint8_t* tags, const int32_t* hs,
-                                  const int64_t* off, int64_t n_items, char* out, int64_t cap, int64_t* out_off,
-                                  int8_t* status) {
-    if (n_items < 0 || !off || !out || !out_off || !status) return -2;
-    int64_t at = 0;
-    out_off[0] = 0;
-    for (int64_t k = 0; k < n_items; ++k) {
-        const int64_t n = off[k + 1] - off[k];
-        if (n < 0) return -2;
-        const int64_t got = tredbam_details_json(seq4, seq4_off, read_len, names, name_off, reads ? reads + off[k] : nullptr,
-                                                 tags ? tags + off[k] : nullptr, hs ? hs + off[k] : nullptr, n, out + at,
-                                                 cap - at);
-        if (got == -3 || got == -2) return got;
-        status[k] = got < 0 ? -1 : 0;
-        if (got > 0) at += got;
-        out_off[k + 1] = at;
-    }
-    return at;
-}
-
-// Mean, population standard deviation and the 40-bin histogram over [0, 1000] of many slices of a pair-length pool
-// (the numbers behind the JSON's PEG / PET / P_PEG / P_PET strings, models.py:87-98 of the reference: mean_std and
-// histogram per list), all loci of a sample in one pass.  Sums run in pool order in double precision.
-int tredbam_pair_stats(const int32_t* pool, const int64_t* first, const int32_t* count, int64_t n, double* mean,
-                       double* sd, int32_t* hist) {
-    if (n < 0 || (n > 0 && (!first || !count || !mean || !sd || !hist))) return -2;
-    constexpr int BINS = 40, SPAN = 1000, WIDTH = SPAN / BINS;
-    for (int64_t k = 0; k < n; ++k) {
-        const int32_t c = count[k];
-        int32_t* h = hist + k * BINS;
-        for (int j = 0; j < BINS; ++j) h[j] = 0;
-        mean[k] = sd[k] = 0;
-        if (c <= 0) continue;
-        if (!pool) return -2;
-        const int32_t* x = pool + first[k];
-        double sum = 0;
-        for (int32_t i = 0; i < c; ++i) sum += (double)x[i];
-        const double m = sum / (double)c;
-        double q = 0;
-        for (int32_t i = 0; i < c; ++i) {
-            const double d = (double)x[i] - m;
-            q += d * d;
-            if (x[i] >= 0 && x[i] <= SPAN) ++h[std::min(x[i] / WIDTH, BINS - 1)];
-        }
-        mean[k] = m;
-        sd[k] = std::sqrt(q / (double)c);
-    }
-    return 0;
-}
-
 int tredbam_max_read_len(tredbam* b, int64_t first_n, int32_t* out) {
     if (!b || !out) return -2;
     int rc = bg_seek(b, b->first_record);
@@ -1311,10 +1146,8 @@ int scan_impl(tredbam* b, const tredbam_site* sites, int32_t n_sites, const tred
         u.read_first = (int64_t)b->sc_read_len.size();
         u.global_first = (int64_t)b->sc_global.size();
         u.target_first = (int64_t)b->sc_target.size();
-        const int64_t win_lo = std::max<int64_t>(0, (int64_t)st.repeat_start - o->pad);
-        const int64_t win_hi = (int64_t)st.repeat_end + o->pad;
-        const int64_t pos_lo = std::max<int64_t>(0, (int64_t)st.repeat_start - o->readlen);
-        const int64_t pos_hi = (int64_t)st.repeat_end + o->readlen;
+        const SiteGeometry g = site_geometry(st, *o);
+        const int64_t win_lo = g.win_lo, win_hi = g.win_hi, pos_lo = g.pos_lo, pos_hi = g.pos_hi, p_lo = g.pe_lo, p_hi = g.pe_hi;
         // ONE walk per locus: the +-pe_reach region of the pair lengths contains the window of the depth and of the
         // read selection, and a region query starts parsing at the beginning of its 16 kb index bin -- three separate
         // walks parsed ~11 000 records per locus to use ~4 500 of them.  A record of the large region is in the
@@ -1325,8 +1158,6 @@ int scan_impl(tredbam* b, const tredbam_site* sites, int32_t n_sites, const tred
         //   read length of the tract; then, from the alternative loci, reads whose MATE lies in the window
         std::unordered_map<std::string, int32_t> names;
         const bool with_pe = o->want_pe != 0;
-        const int64_t p_lo = std::max<int64_t>((int64_t)st.repeat_start - o->pe_reach, 0);
-        const int64_t p_hi = (int64_t)st.repeat_end + o->pe_reach;
         // pair lengths from a walker that went over the +-pe_reach region where the blocks were inflated: it also says
         // between which virtual offsets the window's records lie, and only those are walked here
         const bool hinted = pe && with_pe && pe[i].status == 0 && pe[i].n_global >= 0 && pe[i].n_target >= 0 &&
@@ -1372,8 +1203,7 @@ int scan_impl(tredbam* b, const tredbam_site* sites, int32_t n_sites, const tred
         if (with_pe && !(u.status & TREDBAM_UNIT_FAILED)) {
             const size_t g0 = b->sc_global.size(), t0 = b->sc_target.size();
             int rc;
-            if (wide) rc = n < 0 ? (int)n : pt.finish(b, (int64_t)st.repeat_start - o->flank, (int64_t)st.repeat_end + o->flank,
-                                                       o->span, b->sc_global, b->sc_target);
+            if (wide) rc = n < 0 ? (int)n : pt.finish(b, g.t_lo, g.t_hi, o->span, b->sc_global, b->sc_target);
             else if (hinted) {
                 rc = n < 0 ? (int)n : 0;                                    // computed elsewhere, in the same order
                 if (rc == 0 && (pe[i].global_first < 0 || pe[i].target_first < 0 || pe[i].n_global < 0 || pe[i].n_target < 0 ||
@@ -1385,8 +1215,7 @@ int scan_impl(tredbam* b, const tredbam_site* sites, int32_t n_sites, const tred
                     b->sc_target.insert(b->sc_target.end(), pe_target + pe[i].target_first, pe_target + pe[i].target_first + pe[i].n_target);
                 }
             } else
-                rc = pair_lengths(b, st.tid, p_lo, p_hi, (int64_t)st.repeat_start - o->flank,
-                                  (int64_t)st.repeat_end + o->flank, o->span, b->sc_global, b->sc_target);
+                rc = pair_lengths(b, st.tid, p_lo, p_hi, g.t_lo, g.t_hi, o->span, b->sc_global, b->sc_target);
             if (rc < 0) { b->sc_global.resize(g0); b->sc_target.resize(t0); }
             u.pe_status = (rc == -2 || rc == -4) ? 0 : rc;     // unknown contig / no index: empty lists, as for the reads
             u.n_global = (int32_t)(b->sc_global.size() - g0);
@@ -1433,41 +1262,26 @@ int64_t tredbam_plan_alt_walks(tredbam* b, const tredbam_site* sites, int32_t n_
     if (!b || !o || n_sites < 0 || n_alts < 0 || (n_sites > 0 && !sites) || (n_alts > 0 && (!alts || !tasks)) || cap_chunks < 0 ||
         (cap_chunks > 0 && !chunks))
         return -2;
-    std::unordered_map<int64_t, int32_t> index_of;
-    index_of.reserve(b->plan.size() * 2);
-    for (size_t k = 0; k < b->plan.size(); ++k) index_of[b->plan[k].coffset] = (int32_t)k;
     for (int32_t k = 0; k < n_alts; ++k) { memset(&tasks[k], 0, sizeof tasks[k]); tasks[k].n_chunks = -1; tasks[k].tid = -1; }
-    std::vector<std::pair<uint64_t, uint64_t>> merged;
-    int64_t nc = 0;
+    WalkChunks out{chunks, 0, cap_chunks, {}};
     for (int32_t i = 0; i < n_sites; ++i) {
         const tredbam_site& st = sites[i];
         if (st.tid < 0 || !o->use_alts) continue;
+        const SiteGeometry g = site_geometry(st, *o);
         for (int32_t k = 0; k < st.n_alt; ++k) {
             if (st.alt_first + k < 0 || st.alt_first + k >= n_alts) return -2;
             const tredbam_region& a = alts[st.alt_first + k];
             tredbam_walk_task& t = tasks[st.alt_first + k];
-            t.chunk_first = (int32_t)nc;
-            t.block_end = (int32_t)b->plan.size();
-            int64_t start = a.start, end = a.end;
-            if (a.tid < 0 || region_chunks(b, a.tid, start, end, merged) != 0 || end > INT32_MAX) continue;
-            if ((int64_t)merged.size() > cap_chunks - nc) return -3;
+            const WalkPlan got = plan_task(b, a.tid, a.start, a.end, t, out);
+            if (got == NO_ROOM) return -3;
+            if (got == NOT_WALKABLE) continue;
             t.tid = a.tid;
-            t.start = (int32_t)start;
-            t.end = (int32_t)end;
             t.tstart = st.tid;
-            t.win_lo = (int32_t)std::max<int64_t>(0, (int64_t)st.repeat_start - o->pad);
-            t.win_hi = st.repeat_end + o->pad;
-            for (const auto& ch : merged) {
-                tredbam_walk_chunk& c = chunks[nc++];
-                const auto at = index_of.find((int64_t)(ch.first >> 16));
-                c.begin_block = at == index_of.end() ? -1 : at->second;
-                c.begin_upos = (int32_t)(ch.first & 0xFFFF);
-                c.end_voffset = ch.second;
-            }
-            t.n_chunks = (int32_t)merged.size();
+            t.win_lo = (int32_t)g.win_lo;
+            t.win_hi = (int32_t)g.win_hi;
         }
     }
-    return nc;
+    return out.n;
 }
 
 // The pair walks of tredbam_scan(sites, o) as tasks for a walker that holds the planned blocks inflated (the device:
@@ -1476,43 +1290,23 @@ int64_t tredbam_plan_alt_walks(tredbam* b, const tredbam_site* sites, int32_t n_
 int64_t tredbam_plan_walks(tredbam* b, const tredbam_site* sites, int32_t n_sites, const tredbam_scan_opts* o,
                            tredbam_walk_task* tasks, tredbam_walk_chunk* chunks, int64_t cap_chunks) {
     if (!b || !o || n_sites < 0 || (n_sites > 0 && (!sites || !tasks)) || cap_chunks < 0 || (cap_chunks > 0 && !chunks)) return -2;
-    std::unordered_map<int64_t, int32_t> index_of;
-    index_of.reserve(b->plan.size() * 2);
-    for (size_t k = 0; k < b->plan.size(); ++k) index_of[b->plan[k].coffset] = (int32_t)k;
-    std::vector<std::pair<uint64_t, uint64_t>> merged;
-    int64_t nc = 0;
+    WalkChunks out{chunks, 0, cap_chunks, {}};
     for (int32_t i = 0; i < n_sites; ++i) {
         const tredbam_site& st = sites[i];
+        const SiteGeometry g = site_geometry(st, *o);
         tredbam_walk_task& t = tasks[i];
         memset(&t, 0, sizeof t);
         t.tid = st.tid;
-        t.chunk_first = (int32_t)nc;
-        t.n_chunks = -1;                                   // until proven walkable: the scan computes this site itself
-        t.block_first = 0;
-        t.block_end = (int32_t)b->plan.size();
-        int64_t start = std::max<int64_t>((int64_t)st.repeat_start - o->pe_reach, 0), end = (int64_t)st.repeat_end + o->pe_reach;
-        if (st.tid < 0 || region_chunks(b, st.tid, start, end, merged) != 0) continue;
-        if (end > INT32_MAX || (int64_t)merged.size() > cap_chunks - nc) {
-            if ((int64_t)merged.size() > cap_chunks - nc) return -3;
-            continue;
-        }
-        t.start = (int32_t)start;
-        t.end = (int32_t)end;
-        t.tstart = st.repeat_start - o->flank;
-        t.tend = st.repeat_end + o->flank;
+        const WalkPlan got = plan_task(b, st.tid, g.pe_lo, g.pe_hi, t, out);
+        if (got == NO_ROOM) return -3;
+        if (got == NOT_WALKABLE) continue;                 // (n_chunks -1: the scan computes this site itself)
+        t.tstart = (int32_t)g.t_lo;
+        t.tend = (int32_t)g.t_hi;
         t.span = o->span;
-        t.win_lo = (int32_t)std::max<int64_t>(0, (int64_t)st.repeat_start - o->pad);
-        t.win_hi = st.repeat_end + o->pad;
-        for (const auto& ch : merged) {
-            tredbam_walk_chunk& c = chunks[nc++];
-            const auto at = index_of.find((int64_t)(ch.first >> 16));
-            c.begin_block = at == index_of.end() ? -1 : at->second;
-            c.begin_upos = (int32_t)(ch.first & 0xFFFF);
-            c.end_voffset = ch.second;
-        }
-        t.n_chunks = (int32_t)merged.size();
+        t.win_lo = (int32_t)g.win_lo;
+        t.win_hi = (int32_t)g.win_hi;
     }
-    return nc;
+    return out.n;
 }
 
 // Plain regions as tasks for the same walker: task k = the records overlapping regions[k] = [start, end) of contig tid, its
@@ -1522,34 +1316,18 @@ int64_t tredbam_plan_walks(tredbam* b, const tredbam_site* sites, int32_t n_site
 int64_t tredbam_plan_region_walks(tredbam* b, const tredbam_region* regions, int32_t n_regions, tredbam_walk_task* tasks,
                                   tredbam_walk_chunk* chunks, int64_t cap_chunks) {
     if (!b || n_regions < 0 || (n_regions > 0 && (!regions || !tasks)) || cap_chunks < 0 || (cap_chunks > 0 && !chunks)) return -2;
-    std::unordered_map<int64_t, int32_t> index_of;
-    index_of.reserve(b->plan.size() * 2);
-    for (size_t k = 0; k < b->plan.size(); ++k) index_of[b->plan[k].coffset] = (int32_t)k;
-    std::vector<std::pair<uint64_t, uint64_t>> merged;
-    int64_t nc = 0;
+    WalkChunks out{chunks, 0, cap_chunks, {}};
     for (int32_t i = 0; i < n_regions; ++i) {
-        const tredbam_region& rg = regions[i];
         tredbam_walk_task& t = tasks[i];
         memset(&t, 0, sizeof t);
-        t.tid = rg.tid;
-        t.chunk_first = (int32_t)nc;
-        t.n_chunks = -1;
-        t.block_end = (int32_t)b->plan.size();
-        int64_t start = rg.start, end = rg.end;
-        if (rg.tid < 0 || region_chunks(b, rg.tid, start, end, merged) != 0 || end > INT32_MAX) continue;
-        if ((int64_t)merged.size() > cap_chunks - nc) return -3;
-        t.start = t.win_lo = (int32_t)start;
-        t.end = t.win_hi = (int32_t)end;
-        for (const auto& ch : merged) {
-            tredbam_walk_chunk& c = chunks[nc++];
-            const auto at = index_of.find((int64_t)(ch.first >> 16));
-            c.begin_block = at == index_of.end() ? -1 : at->second;
-            c.begin_upos = (int32_t)(ch.first & 0xFFFF);
-            c.end_voffset = ch.second;
-        }
-        t.n_chunks = (int32_t)merged.size();
+        t.tid = regions[i].tid;
+        const WalkPlan got = plan_task(b, regions[i].tid, regions[i].start, regions[i].end, t, out);
+        if (got == NO_ROOM) return -3;
+        if (got == NOT_WALKABLE) continue;
+        t.win_lo = t.start;                                // (as the query clamps them)
+        t.win_hi = t.end;
     }
-    return nc;
+    return out.n;
 }
 
 // Per planned block, in the plan's (file) order: where it starts in the file, how long it is there, the CRC-32 its
@@ -1577,11 +1355,12 @@ int64_t tredbam_plan(tredbam* b, const tredbam_site* sites, int32_t n_sites, con
                      int64_t* out_bytes) {
     if (!b || !o || n_sites < 0 || (n_sites > 0 && !sites) || n_extra < 0 || (n_extra > 0 && !extra)) return -2;
     b->plan.clear();
+    b->plan_index.clear();
     // `host`: a block the scan reads in any case when the pair lengths and the windows' offsets come from elsewhere
     // (tredbam_scan_pe): bit 0 those of the alternative loci (unless those walks are done elsewhere too:
     // tredbam_scan_walked), bit 1 those of the caller's extra regions.  Which blocks of a +-pe_reach region hold its
     // window's records is known only once the region has been walked (tredbam_walk_result)
-    std::unordered_map<int64_t, size_t> seen;
+    std::unordered_map<int64_t, int32_t>& seen = b->plan_index;      // (places in the order of finding, until the sort below)
     std::vector<std::pair<uint64_t, uint64_t>> merged;
     auto add_region = [&](int32_t tid, int64_t start, int64_t end, uint8_t host) -> int {
         if (region_chunks(b, tid, start, end, merged) != 0) return 0;     // (the scan reports what is wrong with it)
@@ -1606,7 +1385,7 @@ int64_t tredbam_plan(tredbam* b, const tredbam_site* sites, int32_t n_sites, con
             for (int64_t at = (int64_t)(ch.first >> 16); at <= last;) {
                 const auto known = seen.find(at);
                 if (known != seen.end()) {                                 // framed before: only the flag can change
-                    tredbam::Planned& q = b->plan[known->second];
+                    tredbam::Planned& q = b->plan[(size_t)known->second];
                     q.host = (uint8_t)(q.host | host);
                     at += q.clen;
                     continue;
@@ -1616,7 +1395,7 @@ int64_t tredbam_plan(tredbam* b, const tredbam_site* sites, int32_t n_sites, con
                 const int rc = block_frame(b, at, fr, &comp);
                 if (rc <= 0) break;                                        // end of file / damaged frame: left to the scan
                 if (fr.isize > 0) {
-                    seen[at] = b->plan.size();
+                    seen[at] = (int32_t)b->plan.size();
                     b->plan.push_back({at, fr.payload_off, (int32_t)(fr.dlen - 8), fr.clen, fr.crc, fr.isize, host});
                 }
                 at += fr.clen;
@@ -1626,11 +1405,10 @@ int64_t tredbam_plan(tredbam* b, const tredbam_site* sites, int32_t n_sites, con
     };
     for (int32_t i = 0; i < n_sites; ++i) {
         const tredbam_site& st = sites[i];
-        const int64_t win_lo = std::max<int64_t>(0, (int64_t)st.repeat_start - o->pad), win_hi = (int64_t)st.repeat_end + o->pad;
-        const int64_t p_lo = std::max<int64_t>((int64_t)st.repeat_start - o->pe_reach, 0), p_hi = (int64_t)st.repeat_end + o->pe_reach;
         if (st.tid < 0) continue;
-        add_region(st.tid, win_lo, win_hi, 0);
-        if (o->want_pe) add_region(st.tid, p_lo, p_hi, 0);
+        const SiteGeometry g = site_geometry(st, *o);
+        add_region(st.tid, g.win_lo, g.win_hi, 0);
+        if (o->want_pe) add_region(st.tid, g.pe_lo, g.pe_hi, 0);
         if (o->use_alts && alts)
             for (int32_t k = 0; k < st.n_alt; ++k) {
                 const tredbam_region& a = alts[st.alt_first + k];
@@ -1642,6 +1420,8 @@ int64_t tredbam_plan(tredbam* b, const tredbam_site* sites, int32_t n_sites, con
     // in file order: blocks that follow each other in the file then follow each other in the decoder's output, and a
     // record that straddles two of them lies there in one piece (the device's pair walk reads it in place)
     std::sort(b->plan.begin(), b->plan.end(), [](const tredbam::Planned& x, const tredbam::Planned& y) { return x.coffset < y.coffset; });
+    // the plan is finished: compressed offset -> planned block, for the walk planners (plan_task)
+    for (size_t k = 0; k < b->plan.size(); ++k) b->plan_index[b->plan[k].coffset] = (int32_t)k;
     int64_t cb = 0, ob = 0;
     for (const auto& p : b->plan) { cb += ((int64_t)p.payload_len + 3) & ~(int64_t)3; ob += p.isize; }
     if (comp_bytes) *comp_bytes = cb;
@@ -1706,6 +1486,7 @@ void tredbam_preload_clear(tredbam* b, int64_t* hits, int64_t* misses) {
     if (misses) *misses = b->preload_misses;
     b->preloaded.clear();
     b->plan.clear();
+    b->plan_index.clear();
     b->block_coffset = -1; b->block = nullptr; b->block_size = 0; b->block_clen = 0; b->upos = 0;
 }
 

@@ -1,5 +1,7 @@
 // libtredbam.so, second part: a sample's <key>.json and <key>.tred.vcf.gz written natively (include/tredbam.h,
-// tredbam_emit_sample_files).
+// tredbam_emit_sample_files), and the text printers it is made of, which the binding also calls one by one
+// (tredbam_details_json[_many], tredbam_sparse_json[_many], tredbam_float_repr, tredbam_pair_stats).  Nothing here takes
+// a file handle: bamread.cpp is the BGZF / BAM / index / scan / plan layer.
 //
 // What the reference does per sample in Python after its kernels (tredparse/tred.py:251-275 the tredCalls keys, :296-313
 // to_json, :316-374 to_vcf; bam_parser.py:174-182, 248-287 tally / remove_pairs_of_rept; models.py:87-98 mean_std and
@@ -14,6 +16,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <charconv>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -245,6 +248,223 @@ extern "C" {
 const char* tredbam_emit_last_error(void) { return g_emit_error.c_str(); }
 
 double tredbam_pairwise_sum(const double* a, int64_t n) { return (a && n > 0) ? 0.0 + pairwise(a, n) : 0.0; }
+
+// ---- the text printers (include/tredbam.h): no file handle, only the caller's arrays ---------------------------------
+int64_t tredbam_details_json(const uint8_t* seq4, const int64_t* seq4_off, const int32_t* read_len, const char* names,
+                             const int64_t* name_off, const int64_t* reads, const uint8_t* tags, const int32_t* hs,
+                             int64_t n, char* out, int64_t cap) {
+    if (n < 0 || !out || cap < 2 || (n > 0 && (!seq4 || !seq4_off || !read_len || !names || !name_off || !reads || !tags || !hs)))
+        return -2;
+    static const char* const TAGS[6] = {nullptr, "FULL", "PREF", "POST", "REPT", "HANG"};
+    static const char BASES[] = "=ACMGRSVTWYHKDBN";
+    char* p = out;
+    char* const end = out + cap;
+    auto put = [&](const char* s, size_t len) { memcpy(p, s, len); p += len; };
+#define TREDBAM_LIT(S) put(S, sizeof(S) - 1)
+    if (n == 0) { TREDBAM_LIT("[]"); return p - out; }
+    TREDBAM_LIT("[\n");
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t rd = reads[i];
+        const int64_t n0 = name_off[rd], n1 = name_off[rd + 1];
+        const int32_t L = read_len[rd];
+        if (tags[i] < 1 || tags[i] > 5 || L < 0 || n1 < n0) return -2;
+        // worst case of this element: fixed text < 160, the name doubled by escapes, the bases, 11 digits
+        if ((int64_t)(end - p) < 200 + 2 * (n1 - n0) + L) return -3;
+        TREDBAM_LIT("            {\n                \"h\": ");
+        p += snprintf(p, 16, "%d", (int)hs[i]);
+        TREDBAM_LIT(",\n                \"id\": \"");
+        for (int64_t k = n0; k < n1; ++k) {
+            const unsigned char c = (unsigned char)names[k];
+            if (c < 0x20 || c >= 0x7f) return -1;
+            if (c == '"' || c == '\\') *p++ = '\\';
+            *p++ = (char)c;
+        }
+        TREDBAM_LIT("\",\n                \"seq\": \"");
+        const uint8_t* sq = seq4 + seq4_off[rd];
+        {   // two bases per byte of the 4-bit sequence: one table look-up and one 2-byte store per pair
+            static const struct Pairs { char t[256][2]; Pairs() { for (int b = 0; b < 256; ++b) { t[b][0] = BASES[b >> 4]; t[b][1] = BASES[b & 15]; } } } PAIRS;
+            const int32_t whole = L >> 1;
+            for (int32_t k = 0; k < whole; ++k, p += 2) memcpy(p, PAIRS.t[sq[k]], 2);
+            if (L & 1) *p++ = BASES[sq[whole] >> 4];
+        }
+        TREDBAM_LIT("\",\n                \"tag\": \"");
+        put(TAGS[tags[i]], 4);
+        TREDBAM_LIT("\"\n            }");
+        if (i + 1 < n) TREDBAM_LIT(",\n");
+    }
+    if (end - p < 16) return -3;
+    TREDBAM_LIT("\n        ]");
+#undef TREDBAM_LIT
+    return p - out;
+}
+
+// Python's repr(float) (float_repr_style 'short'): the shortest digit string that round-trips -- std::to_chars
+// produces the same digits -- laid out in exponent form when the decimal exponent is <= -5 or >= 16, else positionally
+// with ".0" appended to integers.
+int tredbam_float_repr(double x, char* out) {
+    if (!out || !std::isfinite(x)) return -1;
+    char* p = out;
+    if (std::signbit(x)) { *p++ = '-'; x = -x; }
+    if (x == 0) { memcpy(p, "0.0", 3); return (int)(p - out) + 3; }
+    char sci[40];
+    const auto res = std::to_chars(sci, sci + sizeof sci, x, std::chars_format::scientific);
+    // d[.ddd]e[+-]XX[X]
+    char digits[24];
+    int nd = 0;
+    const char* q = sci;
+    for (; q < res.ptr && *q != 'e'; ++q) if (*q != '.') digits[nd++] = *q;
+    int e10 = 0;
+    {
+        const char* r = q + 1;
+        const bool neg = *r == '-';
+        ++r;
+        for (; r < res.ptr; ++r) e10 = e10 * 10 + (*r - '0');
+        if (neg) e10 = -e10;
+    }
+    if (e10 <= -5 || e10 >= 16) {                      // exponent form: to_chars' own text is Python's
+        const size_t len = (size_t)(res.ptr - sci);
+        memcpy(p, sci, len);
+        return (int)(p - out) + (int)len;
+    }
+    if (e10 >= 0) {
+        for (int i = 0; i <= e10; ++i) *p++ = i < nd ? digits[i] : '0';
+        *p++ = '.';
+        if (nd > e10 + 1) for (int i = e10 + 1; i < nd; ++i) *p++ = digits[i];
+        else *p++ = '0';
+    } else {
+        *p++ = '0'; *p++ = '.';
+        for (int i = 0; i < -e10 - 1; ++i) *p++ = '0';
+        for (int i = 0; i < nd; ++i) *p++ = digits[i];
+    }
+    return (int)(p - out);
+}
+
+namespace {
+inline int key_int(char* out, int32_t v) {                 // decimal text of v (at most 11 bytes), its length
+    char buf[12];
+    char* p = buf + sizeof buf;
+    uint32_t u = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+    do { *--p = (char)('0' + u % 10); u /= 10; } while (u);
+    if (v < 0) *--p = '-';
+    const int n = (int)(buf + sizeof buf - p);
+    memcpy(out, p, (size_t)n);
+    return n;
+}
+}  // namespace
+
+int64_t tredbam_sparse_json(const int32_t* a, const int32_t* b, const double* values, int64_t n, int32_t depth,
+                            char* out, int64_t cap) {
+    if (n < 0 || depth < 0 || depth > 16 || !out || cap < 2 || (n > 0 && (!a || !values))) return -2;
+    char* p = out;
+    char* const end = out + cap;
+    if (n == 0) { memcpy(p, "{}", 2); return 2; }
+    struct Item { char key[24]; int klen; int64_t at; };
+    std::vector<Item> items((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        Item& it = items[(size_t)i];
+        it.klen = key_int(it.key, a[i]);
+        if (b) { it.key[it.klen++] = ','; it.klen += key_int(it.key + it.klen, b[i]); }
+        it.at = i;
+    }
+    std::sort(items.begin(), items.end(), [](const Item& x, const Item& y) {
+        const int c = memcmp(x.key, y.key, (size_t)std::min(x.klen, y.klen));
+        return c != 0 ? c < 0 : x.klen < y.klen;
+    });
+    for (size_t i = 1; i < items.size(); ++i)
+        if (items[i].klen == items[i - 1].klen && memcmp(items[i].key, items[i - 1].key, (size_t)items[i].klen) == 0) return -1;
+    const int pad = 4 * (depth + 1);
+    *p++ = '{'; *p++ = '\n';
+    for (size_t i = 0; i < items.size(); ++i) {
+        if (end - p < pad + 80) return -3;
+        memset(p, ' ', (size_t)pad); p += pad;
+        *p++ = '"';
+        memcpy(p, items[i].key, (size_t)items[i].klen); p += items[i].klen;
+        *p++ = '"'; *p++ = ':'; *p++ = ' ';
+        const int len = tredbam_float_repr(values[items[i].at], p);
+        if (len < 0) return -1;
+        p += len;
+        if (i + 1 < items.size()) *p++ = ',';
+        *p++ = '\n';
+    }
+    if (end - p < 4 * depth + 2) return -3;
+    memset(p, ' ', (size_t)(4 * depth)); p += 4 * depth;
+    *p++ = '}';
+    return p - out;
+}
+
+// Many distributions / many details lists in one call (a sample's 90 + 30 of them: the per-call cost of the binding
+// was a third of the driver thread's time per sample).  Item k covers entries off[k] .. off[k+1] of the input arrays;
+// its text lands at out[out_off[k] .. out_off[k+1]); status[k] = 0, or the single call's -1 (text left empty: the
+// caller's generic encoder takes that item).  Returns the bytes written, -3 when cap is too small, -2 on bad arguments.
+int64_t tredbam_sparse_json_many(const int32_t* a, const int32_t* b, const double* values, const int64_t* off,
+                                 const uint8_t* two_part, int64_t n_items, int32_t depth, char* out, int64_t cap,
+                                 int64_t* out_off, int8_t* status) {
+    if (n_items < 0 || !off || !two_part || !out || !out_off || !status) return -2;
+    int64_t at = 0;
+    out_off[0] = 0;
+    for (int64_t k = 0; k < n_items; ++k) {
+        const int64_t n = off[k + 1] - off[k];
+        if (n < 0 || (two_part[k] && !b)) return -2;
+        const int64_t got = tredbam_sparse_json(a ? a + off[k] : nullptr, two_part[k] ? b + off[k] : nullptr,
+                                                values ? values + off[k] : nullptr, n, depth, out + at, cap - at);
+        if (got == -3 || got == -2) return got;
+        status[k] = got < 0 ? -1 : 0;
+        if (got > 0) at += got;
+        out_off[k + 1] = at;
+    }
+    return at;
+}
+
+int64_t tredbam_details_json_many(const uint8_t* seq4, const int64_t* seq4_off, const int32_t* read_len, const char* names,
+                                  const int64_t* name_off, const int64_t* reads, const uint8_t* tags, const int32_t* hs,
+                                  const int64_t* off, int64_t n_items, char* out, int64_t cap, int64_t* out_off,
+                                  int8_t* status) {
+    if (n_items < 0 || !off || !out || !out_off || !status) return -2;
+    int64_t at = 0;
+    out_off[0] = 0;
+    for (int64_t k = 0; k < n_items; ++k) {
+        const int64_t n = off[k + 1] - off[k];
+        if (n < 0) return -2;
+        const int64_t got = tredbam_details_json(seq4, seq4_off, read_len, names, name_off, reads ? reads + off[k] : nullptr,
+                                                 tags ? tags + off[k] : nullptr, hs ? hs + off[k] : nullptr, n, out + at,
+                                                 cap - at);
+        if (got == -3 || got == -2) return got;
+        status[k] = got < 0 ? -1 : 0;
+        if (got > 0) at += got;
+        out_off[k + 1] = at;
+    }
+    return at;
+}
+
+// Mean, population standard deviation and the 40-bin histogram over [0, 1000] of many slices of a pair-length pool
+// (the numbers behind the JSON's PEG / PET / P_PEG / P_PET strings, models.py:87-98 of the reference: mean_std and
+// histogram per list), all loci of a sample in one pass.  Sums run in pool order in double precision.
+int tredbam_pair_stats(const int32_t* pool, const int64_t* first, const int32_t* count, int64_t n, double* mean,
+                       double* sd, int32_t* hist) {
+    if (n < 0 || (n > 0 && (!first || !count || !mean || !sd || !hist))) return -2;
+    constexpr int BINS = 40, SPAN = 1000, WIDTH = SPAN / BINS;
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t c = count[k];
+        int32_t* h = hist + k * BINS;
+        for (int j = 0; j < BINS; ++j) h[j] = 0;
+        mean[k] = sd[k] = 0;
+        if (c <= 0) continue;
+        if (!pool) return -2;
+        const int32_t* x = pool + first[k];
+        double sum = 0;
+        for (int32_t i = 0; i < c; ++i) sum += (double)x[i];
+        const double m = sum / (double)c;
+        double q = 0;
+        for (int32_t i = 0; i < c; ++i) {
+            const double d = (double)x[i] - m;
+            q += d * d;
+            if (x[i] >= 0 && x[i] <= SPAN) ++h[std::min(x[i] / WIDTH, BINS - 1)];
+        }
+        mean[k] = m;
+        sd[k] = std::sqrt(q / (double)c);
+    }
+    return 0;
+}
 
 int tredbam_emit_sample_files(const tredbam_emit_locus* loci, int32_t n_loci, const tredbam_emit_batch* B,
                               const tredbam_emit_sample* S, const tredbam_emit_opts* O, int32_t* locus_status,

@@ -100,7 +100,7 @@ def _plan_sample(arg, walk=False, select=False):
     """Thread: open the BAM and list the blocks its scan will read -- with walk, also the pair-length regions as tasks
     for the device's walk (bamio plan_walks / plan_blocks); with select, also what the device's read selection needs
     (_select_plan).  Returns the sample's _Plan; None: no GPU help for this sample."""
-    from .bam_parser import DNAPE_ELONGATE, FLANKMATCH, SPAN, _site_arrays, open_bam, y_regions
+    from .bam_parser import _site_arrays, open_bam, y_regions
     o = _options(arg)
     try:
         f = open_bam(o["bam"])
@@ -113,13 +113,12 @@ def _plan_sample(arg, walk=False, select=False):
         loci = [o["repo"][n] for n in o["names"]]
         sites, regions = _site_arrays(o["repo"], o["names"], loci, f)
         sexed = any(t.is_xlinked for t in loci)          # scan_sample then asks for the chrY depth windows too
-        n, cbytes, obytes = f.plan(sites, regions, readlen, pad=SPAN, flank=FLANKMATCH, pe_reach=DNAPE_ELONGATE, span=SPAN,
-                                   use_alts=o["alts"] and not o["clip"], extra=y_regions(o["repo"].ref) if sexed else ())
+        use_alts = o["alts"] and not o["clip"]
+        n, cbytes, obytes = f.plan(sites, regions, readlen, use_alts=use_alts, extra=y_regions(o["repo"].ref) if sexed else ())
         p = _Plan(f, readlen, n, cbytes, obytes)
         if walk and n > 0:
-            p.tasks, p.chunks = f.plan_walks(sites, readlen, pad=SPAN, flank=FLANKMATCH, pe_reach=DNAPE_ELONGATE, span=SPAN)
-            p.alt_tasks, p.alt_chunks = f.plan_alt_walks(sites, regions, readlen, pad=SPAN, flank=FLANKMATCH, pe_reach=DNAPE_ELONGATE,
-                                                         span=SPAN, use_alts=o["alts"] and not o["clip"])
+            p.tasks, p.chunks = f.plan_walks(sites, readlen)
+            p.alt_tasks, p.alt_chunks = f.plan_alt_walks(sites, regions, readlen, use_alts=use_alts)
             p.coffset, p.clen, p.crc, p.host = f.plan_blocks()
             p.select = _select_plan(o, f, loci, sites, regions, readlen, sexed, p) if select else None
         return p
@@ -137,19 +136,18 @@ def _select_plan(o, f, loci, sites, regions, readlen, sexed, p):
     locus the file or the kernels cannot serve (its contig is missing, its template ladder or the reads are too long)."""
     import numpy as np
     from ._lib import SELECT_TASK_DTYPE
-    from .bam_parser import MAX_READ_LEN, MAX_TEMPLATE_LEN, y_regions
+    from .bam_parser import MAX_READ_LEN, ladder_fits, selection_range, y_regions
     if o["log"] == "DEBUG" or o["alignments"] or o["consensus"] or not (o["repeatpairs"] or o["clip"]):
         return None
     if len(sites) == 0 or (sites["tid"] < 0).any() or (p.tasks["n_chunks"] < 0).any() or readlen > MAX_READ_LEN:
         return None
-    if any(len(t.prefix) + t.period * -(-readlen // t.period) + len(t.suffix) > MAX_TEMPLATE_LEN for t in loci):
+    if not all(ladder_fits(t, readlen) for t in loci):
         return None
     use_alts = o["alts"] and not o["clip"]
     if use_alts and len(regions) and ((p.alt_tasks["n_chunks"] < 0) & (regions["tid"][:len(p.alt_tasks)] >= 0)).any():
         return None                                    # (a region of a contig the file HAS that cannot be walked from the plan)
     sel = np.zeros(len(sites), SELECT_TASK_DTYPE)
-    sel["pos_lo"] = np.maximum(sites["repeat_start"].astype(np.int64) - readlen, 0)
-    sel["pos_hi"] = sites["repeat_end"].astype(np.int64) + readlen
+    sel["pos_lo"], sel["pos_hi"] = selection_range(sites, readlen)
     sel["alt_first"], sel["n_alt"] = sites["alt_first"], (sites["n_alt"] if use_alts else 0)
     ytasks = ychunks = ywidth = None
     if sexed:
@@ -241,7 +239,7 @@ def _device_scan(arg, p, dev, res, selres):
     depth, the read count and the slices of the call's pair-length pools."""
     import numpy as np
     from . import bamio
-    from .bam_parser import SPAN, SampleScan
+    from .bam_parser import SampleScan, window_widths
     o = _options(arg)
     sp = p.select
     s = SampleScan()
@@ -260,8 +258,7 @@ def _device_scan(arg, p, dev, res, selres):
     u["n_global"], u["n_target"] = r["n_global"], r["n_target"]
     u["global_first"], u["target_first"] = r["global_first"], r["target_first"]
     s.global_lens, s.target_lens = dev.gp, dev.tp
-    window = np.array([x.repeat_end + SPAN - max(0, x.repeat_start - SPAN) + 1 for x in s.loci], np.float64)
-    s.depth = u["depth_sum"] / window
+    s.depth = u["depth_sum"] / window_widths(s.loci)
     s.ploidy = np.array([1 if (s.gender == "Male" and x.is_xlinked) else x.ploidy for x in s.loci], np.int32)
     s.packed = s.word_off = s.read_len = s.seq4 = s.seq4_off = s.name_blob = s.name_off = s.name_id = None
     s.dropped = {}
