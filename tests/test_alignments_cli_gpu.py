@@ -43,10 +43,11 @@ def test_engine_alignments_agree_with_the_tags_the_reads_were_counted_for(engine
     and whose operations consume exactly the aligned bases."""
     from tredparse_amd import _lib
     from tredparse_amd.runtime import collect_sample
-    from tredparse_amd.tred import TREDsRepo, _alignment_units
+    from tredparse_amd.engine import PackedUnits
+    from tredparse_amd.tred import TREDsRepo
     repo = TREDsRepo(ref="hg38")
     scan = collect_sample(("t001", os.path.join(GOLD, "bam", "t001.bam"), repo, ["HD"], 300, False, False, True, True, "INFO"))
-    units = _alignment_units([(0, scan, [0])], False)
+    units = PackedUnits.from_scans([(scan, [0])])
     tag, h, _, _, _ = engine.classify(units)
     engine.ctx.reset_timing()
     al = engine.alignments(units)[0]

@@ -8,7 +8,7 @@ import os
 import pytest
 
 from tredparse_amd import _lib, synth, synth_bam, tred as tredmod
-from tredparse_amd.engine import Engine
+from tredparse_amd.engine import Engine, PackedUnits
 
 from .test_long_reads_e2e_gpu import LONG_SAMPLES
 
@@ -49,7 +49,7 @@ def test_engine_alignments_of_long_reads_are_the_references(long_engine, bam, go
     ks = [k for k, n in enumerate(scan.names) if n in golden]
     assert len(ks) == len(golden) == 2
     long_engine.ctx.reset_timing()
-    res = long_engine.alignments(tredmod._alignment_units([(0, scan, ks)], False))
+    res = long_engine.alignments(PackedUnits.from_scans([(scan, ks)]))
     assert long_engine.ctx.get_timing(_lib.KERNEL_CIGAR_LONG)[0] == 1          # ONE long call for all winners
     for k, al in zip(ks, res):
         rows = golden[scan.names[k]]

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tredparse_amd import _lib, synth, synth_bam, tred as tredmod
-from tredparse_amd.engine import Engine, Unit
+from tredparse_amd.engine import Engine, PackedUnits, Unit
 from tredparse_amd.meta import TREDsRepo
 
 from . import pileup_model as pm
@@ -58,7 +58,7 @@ def _same(x, T, table, want, reads):
 def _t001_units():
     from tredparse_amd.runtime import collect_sample
     scan = collect_sample(T001 + (TREDsRepo(ref="hg38"), ["HD"], 300, False, False, True, True, "INFO"))
-    return tredmod._alignment_units([(0, scan, [0])], False)
+    return PackedUnits.from_scans([(scan, [0])])
 
 
 def test_t001_hd_equals_the_pileup_of_the_golden_reports_text(engine, t001_want):
@@ -167,7 +167,7 @@ def test_long_reads_consensus_equals_the_model(long_bam):
         scan = tredmod.collect_sample((NAME, long_bam, repo, LONG_SAMPLES[NAME][0], 300, False, False, True, True, "INFO"),
                                       long_reads=True)
         ks = [k for k, n in enumerate(scan.names) if n in golden]
-        units = tredmod._alignment_units([(0, scan, ks)], False)
+        units = PackedUnits.from_scans([(scan, ks)])
         w = e.winners(units)
         al = e.alignments(units, winners=w)
         alleles = [sorted({x.h for x in a.values() if x.tag == _lib.TAG_FULL}) + [299] for a in al]
@@ -175,10 +175,10 @@ def test_long_reads_consensus_equals_the_model(long_bam):
         res = e.consensus(units, alleles, winners=w)
         assert e.ctx.get_timing(_lib.KERNEL_PILEUP)[0] == 1
         spanned = 0
-        for u, a, r, want in zip(units, al, res, alleles):
+        for k, a, r, want in zip(ks, al, res, alleles):
             assert sorted(r) == want
             for h in want:
-                t = u.tred
+                t = scan.loci[k]
                 T = t.prefix + t.repeat * h + t.suffix
                 table, n = pm.table(len(T)), 0
                 for x in a.values():

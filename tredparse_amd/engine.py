@@ -41,10 +41,7 @@ class Unit(object):
         self.fullsearch = bool(fullsearch)
         self.clip = bool(clip)
         self.read_pair_ids = read_pair_ids  # only for --norepeatpairs
-        period = len(tred.repeat)
-        self.max_units = -(-self.readlen // period)          # bam_parser.py:73
-        self.ref_len = tred.repeat_end - tred.repeat_start + 1  # bam_parser.py:68
-        self.minpe = tred.repeat_end - tred.repeat_start + 2 * 9 + 2   # bam_parser.py:361
+        self.max_units = -(-self.readlen // len(tred.repeat))          # bam_parser.py:73
 
 
 JOINT_CAP = 512   # sparse joint entries per unit asked for first (pairs with exp(ml - max) >= e^-10)
@@ -52,20 +49,71 @@ JOINT_CAP = 512   # sparse joint entries per unit asked for first (pairs with ex
 
 class PackedUnits(object):
     """A batch of sample x locus units already in the C ABI's layout (include/tredgpu.h): what
-    bam_parser.scan_sample produces, concatenated over samples.  No read strings, no per-read Python objects.
+    bam_parser.scan_sample produces, concatenated over samples (from_scans: no read strings, no per-read Python objects),
+    or a list of Unit (from_units).  The one form every Engine entry point works on.
 
       packed / read_off / read_len          the reads, unit after unit
       unit_read_off, ladder_keys[unit]      reads of each unit; its template ladder (prefix, repeat, suffix, max_units)
       params (UNIT_DTYPE)                   grid inputs; pe_off / tl_off index global_lens / target_lens
       pair_id                               per read, for --norepeatpairs (None otherwise)
+      text(i)                               read i as text
     """
+
+    @classmethod
+    def from_units(cls, units):
+        """units: [Unit].  The only place that turns Unit objects into the C ABI's arrays; the reads are packed once."""
+        units = list(units)
+        clips = set(u.clip for u in units)
+        if len(clips) > 1:
+            raise ValueError("all units of one batch must share the clip setting")
+        b = cls()
+        b.clip, b._picks = (clips.pop() if clips else False), None
+        b._texts = [r for u in units for r in u.reads]
+        b.packed, b.read_off, b.read_len = _lib.pack_reads(b._texts)
+        b.n_units, b.n_reads = len(units), len(b._texts)
+        b.unit_read_off = np.zeros(b.n_units + 1, np.int32)
+        b.unit_read_off[1:] = np.cumsum([len(u.reads) for u in units])
+        b.pair_id = None
+        if any(u.read_pair_ids is not None for u in units):       # (a unit without ids: -1 for its reads)
+            b.pair_id = np.concatenate([np.asarray(u.read_pair_ids if u.read_pair_ids is not None
+                                                   else -np.ones(len(u.reads)), np.int32) for u in units])
+        b.ladder_keys = [(u.tred.prefix, u.tred.repeat, u.tred.suffix, u.max_units) for u in units]
+        b.max_units = max([k[3] for k in b.ladder_keys] + [1])
+        g = np.array([len(u.global_lens) for u in units], np.int64)
+        t = np.array([len(u.target_lens) for u in units], np.int64)
+        b.global_lens = np.asarray([x for u in units for x in u.global_lens], np.int32)
+        b.target_lens = np.asarray([x for u in units for x in u.target_lens], np.int32)
+        cols = np.array([(len(u.tred.repeat), u.readlen, u.ploidy, u.maxinsert, u.fullsearch, u.tred.repeat_end - u.tred.repeat_start,
+                          u.tred.cutoff_risk, u.tred.is_expansion, u.tred.is_recessive) for u in units], np.int32).reshape(-1, 9).T
+        b.params = _rows(*cols, np.cumsum(g) - g, g, np.cumsum(t) - t, t, np.array([u.depth for u in units], np.float64))
+        return b
+
+    def text(self, i):
+        """Read i of the batch as text: the unit's own string (from_units), or what the scan's record decodes to
+        (from_scans; the picks' read indices are put together on the first call)."""
+        if self._picks is None:
+            return self._texts[i]
+        if self._texts is None:
+            ends, parts = [], []            # per pick with loci: where its reads end in the batch; (scan, their pool indices)
+            for scan, ks in self._picks:
+                if len(ks):
+                    u = scan.unit[np.asarray(ks, np.int64)]
+                    parts.append((scan, _ranges(u["read_first"].astype(np.int64), u["n_reads"].astype(np.int64), force=True)))
+                    ends.append(len(parts[-1][1]) + (ends[-1] if ends else 0))
+            self._texts = (np.asarray(ends, np.int64), parts)
+        ends, parts = self._texts
+        p = int(np.searchsorted(ends, i, side="right"))
+        scan, reads = parts[p]
+        return scan.sequence(int(reads[i - (int(ends[p - 1]) if p else 0)]))
 
     @classmethod
     def from_scans(cls, picks, maxinsert=300, fullsearch=False, clip=False, repeatpairs=True):
         """picks: [(SampleScan, [locus indices])] -- the listed loci of each scan, in that order.  One pass of array
-        operations per scan (a unit at a time in Python this cost a driver 0.6-1.2 ms per sample, 30 units each)."""
+        operations per scan (a unit at a time in Python this cost a driver 0.6-1.2 ms per sample, 30 units each).  The
+        batch keeps a reference to picks for text(): the scans live as long as the batch (and a BatchResult of it), and
+        the caller must not change the lists afterwards."""
         b = cls()
-        b.clip, b.ladder_keys = bool(clip), []
+        b.clip, b.ladder_keys, b._picks, b._texts = bool(clip), [], picks, None
         words, offs, lens, ids, gls, tls, rows, counts = [], [np.zeros(1, np.int64)], [], [], [], [], [], []
         wbase = n_gl = n_tl = 0
         for scan, ks in picks:
@@ -166,14 +214,23 @@ def _unit_rows(scan, ks, maxinsert, fullsearch, pe_off, tl_off):
     """The grid inputs (UNIT_DTYPE rows) of a scan's loci ks; pe_off / tl_off: where each unit's pair lengths start in the
     call's global_lens / target_lens."""
     st, u = _static(scan), scan.unit[ks]
-    r = np.zeros(len(ks), _lib.UNIT_DTYPE)
-    r["period"], r["readlen"], r["ploidy"] = st["period"][ks], scan.readlen, scan.ploidy[ks]
-    r["maxinsert"], r["fullsearch"] = maxinsert, int(fullsearch)
-    r["ref_len"], r["minpe"] = st["span"][ks] + 1, st["span"][ks] + 20
-    r["cutoff_risk"], r["is_expansion"], r["is_recessive"] = st["cutoff_risk"][ks], st["is_expansion"][ks], st["is_recessive"][ks]
-    r["pe_off"], r["n_global"] = pe_off, u["n_global"]
-    r["tl_off"], r["n_target"] = tl_off, u["n_target"]
-    r["half_depth"] = np.asarray(scan.depth, np.float64)[ks] / 2
+    return _rows(st["period"][ks], scan.readlen, scan.ploidy[ks], maxinsert, fullsearch, st["span"][ks], st["cutoff_risk"][ks],
+                 st["is_expansion"][ks], st["is_recessive"][ks], pe_off, u["n_global"], tl_off, u["n_target"],
+                 np.asarray(scan.depth, np.float64)[ks])
+
+
+def _rows(period, readlen, ploidy, maxinsert, fullsearch, span, cutoff_risk, is_expansion, is_recessive, pe_off, n_global,
+          tl_off, n_target, depth):
+    """UNIT_DTYPE rows from columns (arrays, one entry per unit, or scalars): the one place that builds them.  span: the
+    tract's repeat_end - repeat_start."""
+    r = np.zeros(len(period), _lib.UNIT_DTYPE)
+    r["period"], r["readlen"], r["ploidy"] = period, readlen, ploidy
+    r["maxinsert"], r["fullsearch"] = maxinsert, np.asarray(fullsearch, np.int32)
+    r["ref_len"], r["minpe"] = span + 1, span + 2 * 9 + 2          # bam_parser.py:68, :361
+    r["cutoff_risk"], r["is_expansion"], r["is_recessive"] = cutoff_risk, is_expansion, is_recessive
+    r["pe_off"], r["n_global"] = pe_off, n_global
+    r["tl_off"], r["n_target"] = tl_off, n_target
+    r["half_depth"] = depth / 2
     return r
 
 
@@ -225,13 +282,15 @@ class BatchResult(object):
         a, e = int(b.unit_read_off[i]), int(b.unit_read_off[i + 1])
         r = UnitResult()
         r.tags, r.hs, r.scores = self.tag[a:e], self.h[a:e], self.score[a:e]
-        r.full = r.pref = r.rept_hist = None
+        r.full = r.pref = r.rept_hist = None      # the histograms {units: count}: only where the batch has them (not the fused calls)
+        if getattr(self, "full", None) is not None:
+            r.full, r.pref, r.rept_hist = ({int(k): int(v) for k, v in enumerate(x[i]) if v} for x in (self.full, self.pref, self.rept))
         r.rept = int(self.rept[i].sum())
         r.call = self.calls[i]
         r.grid = None
         if getattr(self, "grid", None) is not None and self.calls[i]["status"] == 0:
             r.grid = self.grid[self.grid_off[i]:self.grid_off[i] + self.calls[i]["n_pairs"]]
-        r.joint = self.joint[i] if self.calls[i]["status"] == 0 else None
+        r.joint = self.joint[i] if self.calls[i]["status"] == 0 and self.joint is not None else None
         ju = getattr(self, "joint_units", None)
         r.joint_units = None
         if ju is not None and self.calls[i]["status"] == 0:
@@ -253,11 +312,12 @@ class UnitResult(object):
 
 
 class _Winners(object):
-    """Engine.winners' result: per tagged read of the units (m of them, in batch order) tag, h, the read's index in the
-    batch (items), the winning template (win, db order) and its dump row (best), the unit (unit_of), the read's text; and
-    the arguments and outputs of the sw_cigar call over them (item_ladder, fields, ops, n_ops, cap).  uro: the units' read
-    offsets.  Without a tagged read only items (empty) and uro are set."""
-    __slots__ = ("tag", "h", "uro", "items", "win", "best", "unit_of", "reads", "item_ladder", "fields", "ops", "n_ops", "cap")
+    """Engine.winners' result: the batch, and per tagged read of its units (m of them, in batch order) tag, h, the read's
+    index in the batch (items), the winning template (win, db order) and its dump row (best), the unit (unit_of); and the
+    arguments and outputs of the sw_cigar call over them (packed / read_off / read_len: the tagged reads gathered from the
+    batch, item_ladder, fields, ops, n_ops, cap).  Without a tagged read only batch and items (empty) are set."""
+    __slots__ = ("batch", "tag", "h", "items", "win", "best", "unit_of", "packed", "read_off", "read_len", "item_ladder",
+                 "fields", "ops", "n_ops", "cap")
 
 
 class ReadAlignment(object):
@@ -305,14 +365,15 @@ class Engine(object):
             self._ladders = known
         return np.asarray([index[k] for k in keys], np.int32)
 
-    def classify_packed(self, b):
-        """SW + tagging of a PackedUnits batch: (tag u8[], h i16[], score i16[]) per read."""
+    def classify_packed(self, b, dump=None):
+        """SW + tagging of a PackedUnits batch: (tag u8[], h i16[], score i16[]) per read.  dump: i16 [reads][templates][6]
+        to fill with every (read, template) pair's row, in db order."""
         n = b.n_reads
         tag, h, sc = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int16), np.zeros(max(n, 1), np.int16)
         if n:
             lad = self._register(b.ladder_keys)
             self.ctx.sw_classify(_lib.MEM_HOST, b.packed, b.read_off, b.read_len, n, b.unit_read_off, lad, b.n_units,
-                                 _lib.default_sw_params(clip=b.clip), tag, h, sc, None, 0)
+                                 _lib.default_sw_params(clip=b.clip), tag, h, sc, dump, dump.shape[1] if dump is not None else 0)
         return tag[:n], h[:n], sc[:n]
 
     def genotype_packed(self, b, dense=False):
@@ -413,19 +474,22 @@ class Engine(object):
         r.tag, r.h, r.score = r.tag[:n], r.h[:n], r.score[:n]
         return r
 
-    def _genotype_packed_stepwise(self, b, dense=False):
-        """genotype_packed through the three separate calls (SW, tally, grid)."""
+    def _genotype_packed_stepwise(self, b, dense=False, joint=True, refuse_invalid=False):
+        """genotype_packed through the three separate calls (SW, tally, grid); joint=False: no joint distribution;
+        refuse_invalid: raise straight after the SW call when a read came back TAG_INVALID."""
         r = BatchResult()
         r.batch = b
         r.grid = r.grid_off = None
         r.tag, r.h, r.score = self.classify_packed(b)
+        if refuse_invalid:
+            _refuse_invalid(r.tag)
         g, n = b.n_units, b.n_reads
         hs = b.max_units + 2
         r.full, r.pref, r.rept = (np.zeros((g, hs), np.int32) for _ in range(3))
         self.ctx.tally(_lib.MEM_HOST, r.tag if n else np.zeros(1, np.uint8), r.h if n else np.zeros(1, np.int16), n,
                        b.unit_read_off, g, b.pair_id if n else None, hs, r.full, r.pref, r.rept)
         hist = (b.params, hs, r.full, r.pref, r.rept, b.global_lens, b.target_lens)
-        r.calls, r.marg, r.joint, r.joint_units = self._grid_arrays(*hist)
+        r.calls, r.marg, r.joint, r.joint_units = self._grid_arrays(*hist, joint=joint)
         if dense and g:
             r.grid, r.grid_off = self._dense_dump(*hist, r.calls)
         return r
@@ -454,51 +518,30 @@ class Engine(object):
                                  np.zeros(g, _lib.CALL_DTYPE), grid_off, grid, None, 0)
         return grid, grid_off
 
-    # ---- (1) SW + tagging only -----------------------------------------------------------------------
+    # ---- lists of Unit: packed once (PackedUnits.from_units), then the packed path ------------------------------
     def classify(self, units, want_dump=False):
-        """Per unit: (tags u8[], h i16[], score i16[]) [+ dump].  units: list of Unit."""
-        ladders, lad_index, unit_ladder = [], {}, []
-        for u in units:
-            key = (u.tred.prefix, u.tred.repeat, u.tred.suffix, u.max_units)
-            if key not in lad_index:
-                lad_index[key] = len(ladders)
-                ladders.append(key)
-            unit_ladder.append(lad_index[key])
-        if self._ladders != ladders:
-            self.ctx.set_ladders(ladders)
-            self._ladders = ladders
-        reads = [r for u in units for r in u.reads]
-        packed, woff, rlen = _lib.pack_reads(reads)
-        n = len(reads)
-        uro = np.zeros(len(units) + 1, np.int32)
-        uro[1:] = np.cumsum([len(u.reads) for u in units])
-        tag = np.zeros(max(n, 1), np.uint8)
-        h = np.zeros(max(n, 1), np.int16)
-        sc = np.zeros(max(n, 1), np.int16)
-        nt = max([2 * l[3] for l in ladders] + [1])
+        """SW + tagging of units (a list of Unit, or a PackedUnits): (tag u8[], h i16[], score i16[], the units' read
+        offsets, dump or None) -- classify_packed, with every (read, template) pair's row when want_dump."""
+        b = _batch(units)
+        n = b.n_reads
+        nt = max([2 * k[3] for k in b.ladder_keys] + [1])
         dump = np.zeros((max(n, 1), nt, 6), np.int16) if want_dump else None
-        clips = set(u.clip for u in units)
-        if len(clips) > 1:
-            raise ValueError("all units of one batch must share the clip setting")
-        params = _lib.default_sw_params(clip=clips.pop() if clips else False)
-        if n:
-            self.ctx.sw_classify(_lib.MEM_HOST, packed, woff, rlen, n, uro, np.asarray(unit_ladder, np.int32),
-                                 len(units), params, tag, h, sc, dump, nt if want_dump else 0)
-        if (tag[:n] == _lib.TAG_INVALID).any():
-            raise _lib.TredGpuError("a read exceeds TREDGPU_MAX_READ_LEN")
-        return tag[:n], h[:n], sc[:n], uro, (dump[:n] if want_dump else None)
+        tag, h, sc = self.classify_packed(b, dump)
+        _refuse_invalid(tag)
+        return tag, h, sc, b.unit_read_off, (dump[:n] if want_dump else None)
 
-    # ---- (1b) the alignment behind every tagged read --------------------------------------------------
+    # ---- the alignment behind every tagged read -------------------------------------------------------
     def winners(self, units):
         """What alignments and consensus share: classify with the dump, then per tagged read (HANG included) the winning
         dump row -- the highest score, then the fewest units, then the first row in db order (bam_parser.py:174), which is
-        the pair out_tag / out_h stand for -- and ONE sw_cigar call for all winners.  Returns a _Winners: hand it to both
-        when both are wanted, so that these steps run once."""
-        tag, h, sc, uro, dump = self.classify(units, want_dump=True)
+        the pair out_tag / out_h stand for -- and ONE sw_cigar call for all winners, their packed words gathered from the
+        batch.  Returns a _Winners: hand it to both when both are wanted, so that these steps run once."""
+        b = _batch(units)
+        tag, h, sc, uro, dump = self.classify(b, want_dump=True)
         items = np.nonzero(tag != _lib.TAG_NONE)[0]
         m = len(items)
         w = _Winners()
-        w.items, w.uro = items, uro
+        w.batch, w.items = b, items
         if m == 0:                            # (no tagged read: nothing was asked of sw_cigar)
             return w
         # rows in db order are u=1 fwd, u=1 rc, u=2 fwd, ...: the first row with the highest score has the fewest units
@@ -509,18 +552,14 @@ class Engine(object):
         assert (best[:, 0] == sc[items]).all() and (best[:, 5] == tag[items]).all() and (win // 2 + 1 == h[items]).all(), \
             "the winning dump row is not the pair the read was tagged for"
         unit_of = (np.searchsorted(uro, items, side="right") - 1).astype(np.int64)
-        lad_index = {k: i for i, k in enumerate(self._ladders)}
-        unit_ladder = np.asarray([lad_index[(u.tred.prefix, u.tred.repeat, u.tred.suffix, u.max_units)] for u in units], np.int32)
-        reads = [units[g].reads[i - int(uro[g])] for g, i in zip(unit_of.tolist(), items.tolist())]
-        packed, woff, rlen = _lib.pack_reads(reads)
+        w.packed, w.read_off, w.read_len = _gather_reads(b.packed, b.read_off, b.read_len, items)
         fields = np.ascontiguousarray(best[:, :5], np.int16)
-        item_ladder = np.ascontiguousarray(unit_ladder[unit_of])
-        clip = bool(units[0].clip)
+        item_ladder = np.ascontiguousarray(self._register(b.ladder_keys)[unit_of])
         cap = 32
         while True:
             ops, n_ops, status = np.zeros((m, cap), np.uint32), np.zeros(m, np.int32), np.zeros(m, np.int32)
-            self.ctx.sw_cigar(_lib.MEM_HOST, packed, woff, rlen, m, item_ladder, win, fields,
-                              _lib.default_sw_params(clip=clip), cap, ops, n_ops, status, ladders=self._ladders)
+            self.ctx.sw_cigar(_lib.MEM_HOST, w.packed, w.read_off, w.read_len, m, item_ladder, win, fields,
+                              _lib.default_sw_params(clip=b.clip), cap, ops, n_ops, status, ladders=self._ladders)
             if not (status == _lib.CIGAR_OVERFLOW).any():
                 break
             cap = int(n_ops.max())            # (a CIGAR of more than 32 operations: once more with the room it needs)
@@ -528,29 +567,31 @@ class Engine(object):
             k = int(np.nonzero(status != _lib.CIGAR_OK)[0][0])
             raise _lib.TredGpuError("sw_cigar: status {} for read {} of unit {}".format(int(status[k]), int(items[k] - uro[unit_of[k]]),
                                                                                       int(unit_of[k])))
-        w.tag, w.h, w.win, w.best, w.unit_of, w.reads = tag[items], h[items], win, best, unit_of, reads
+        w.tag, w.h, w.win, w.best, w.unit_of = tag[items], h[items], win, best, unit_of
         w.item_ladder, w.fields, w.ops, w.n_ops, w.cap = item_ladder, fields, ops, n_ops, cap
         return w
 
     def alignments(self, units, winners=None):
         """Per unit: {read index in the unit: ReadAlignment} for every tagged read (HANG included): the pair the read was
-        tagged for and its CIGAR (winners: what self.winners(units) returned, when the caller already has it)."""
+        tagged for and its CIGAR (winners: what self.winners(units) returned, when the caller already has it).  Only
+        these reads are turned into text."""
         from .bam_parser import rc
         from .ssw import PyAlignRes
         w = self.winners(units) if winners is None else winners
-        out = [{} for _ in units]
+        b = w.batch
+        out = [{} for _ in range(b.n_units)]
         targets = {}
         for j in range(len(w.items)):
-            g, t = int(w.unit_of[j]), int(w.win[j])
+            g, t, i = int(w.unit_of[j]), int(w.win[j]), int(w.items[j])
             if (g, t) not in targets:
-                x = units[g].tred
-                text = x.prefix + x.repeat * (t // 2 + 1) + x.suffix
+                prefix, repeat, suffix, _ = b.ladder_keys[g]
+                text = prefix + repeat * (t // 2 + 1) + suffix
                 targets[(g, t)] = rc(text) if t % 2 else text
-            al = PyAlignRes(w.best[j], w.reads[j], targets[(g, t)], w.ops[j, :w.n_ops[j]])
-            out[g][int(w.items[j] - w.uro[g])] = ReadAlignment(int(w.tag[j]), int(w.h[j]), t % 2, targets[(g, t)], al)
+            al = PyAlignRes(w.best[j], b.text(i), targets[(g, t)], w.ops[j, :w.n_ops[j]])
+            out[g][i - int(b.unit_read_off[g])] = ReadAlignment(int(w.tag[j]), int(w.h[j]), t % 2, targets[(g, t)], al)
         return out
 
-    # ---- (1c) what is in the tract of an allele ---------------------------------------------------------
+    # ---- what is in the tract of an allele --------------------------------------------------------------
     def consensus(self, units, alleles, winners=None):
         """Per unit: {a: consensus.AlleleConsensus} for every a >= 1 of alleles[unit] (repeat units): the reads of the
         unit tagged FULL with h == a, laid on prefix + repeat * a + suffix by the alignments of self.winners (winners:
@@ -561,16 +602,17 @@ class Engine(object):
         its template in lower case and empty lists."""
         from .consensus import AlleleConsensus
         w = self.winners(units) if winners is None else winners
+        b = w.batch
         group_of, groups = {}, []
         for g, want in enumerate(alleles):
             for a in sorted(set(int(x) for x in want)):
                 if a >= 1:
                     group_of[(g, a)] = len(groups)
                     groups.append((g, a))
-        out = [{} for _ in units]
+        out = [{} for _ in range(b.n_units)]
         if not groups:
             return out
-        stride = max(self.ctx._template_len(l) for l in self._ladders) + 1
+        stride = max(self.ctx._template_len(l) for l in self._ladders) + 1       # (of the table the call is given, not the batch's own)
         counts, n_reads = None, np.zeros(len(groups), np.int64)
         if len(w.items):
             gid = np.array([group_of.get((g, a), -1) if t == _lib.TAG_FULL else -1
@@ -578,7 +620,7 @@ class Engine(object):
             sel = np.nonzero(gid >= 0)[0]
             m = len(sel)
             if m:
-                packed, woff, rlen = _lib.pack_reads([w.reads[j] for j in sel.tolist()])
+                packed, woff, rlen = _gather_reads(w.packed, w.read_off, w.read_len, sel)
                 counts = np.zeros((len(groups), stride, _lib.PILEUP_CHANNELS), np.int32)
                 status = np.zeros(m, np.int32)
                 arr = lambda x, dt: np.ascontiguousarray(x[sel], dt)
@@ -589,85 +631,60 @@ class Engine(object):
                     k = int(np.nonzero(status != _lib.PILEUP_OK)[0][0])
                     j = int(sel[k])
                     raise _lib.TredGpuError("pileup: status {} for read {} of unit {}".format(
-                        int(status[k]), int(w.items[j] - w.uro[w.unit_of[j]]), int(w.unit_of[j])))
+                        int(status[k]), int(w.items[j] - b.unit_read_off[w.unit_of[j]]), int(w.unit_of[j])))
                 n_reads = np.bincount(gid[sel], minlength=len(groups))
         for k, (g, a) in enumerate(groups):
-            x = units[g].tred
-            T = x.prefix + x.repeat * a + x.suffix
+            prefix, repeat, suffix, _ = b.ladder_keys[g]
+            T = prefix + repeat * a + suffix
             table = np.zeros((len(T) + 1, _lib.PILEUP_CHANNELS), np.int32)
             if n_reads[k]:
                 table[:] = counts[k, :len(T) + 1]          # (a group with reads has a template of the ladder: it fits the stride)
-            out[g][a] = AlleleConsensus(a, n_reads[k], table, T, len(x.prefix), len(x.repeat))
+            out[g][a] = AlleleConsensus(a, n_reads[k], table, T, len(prefix), len(repeat))
         return out
 
     # ---- the whole path ------------------------------------------------------------------------------
     def genotype(self, units, want_grid=True):
-        """SW + tagging -> histograms -> likelihood grid for a batch of units; returns [UnitResult]."""
-        if not units:
-            return []
-        tag, h, sc, uro, _ = self.classify(units)
-        n, g = len(tag), len(units)
-        hs = max(u.max_units for u in units) + 2
-        full = np.zeros((g, hs), np.int32)
-        pref = np.zeros((g, hs), np.int32)
-        rept = np.zeros((g, hs), np.int32)
-        pair_ids = None
-        if any(u.read_pair_ids is not None for u in units):
-            pair_ids = np.concatenate([np.asarray(u.read_pair_ids if u.read_pair_ids is not None
-                                                  else -np.ones(len(u.reads)), np.int32) for u in units])
-        self.ctx.tally(_lib.MEM_HOST, tag if n else np.zeros(1, np.uint8), h if n else np.zeros(1, np.int16), n, uro,
-                       g, pair_ids, hs, full, pref, rept)
-        calls, marg, dump, goff, joint = self._grid(units, hs, full, pref, rept, want_grid)
-        out = []
-        for i, u in enumerate(units):
-            r = UnitResult()
-            r.tags, r.hs, r.scores = tag[uro[i]:uro[i + 1]], h[uro[i]:uro[i + 1]], sc[uro[i]:uro[i + 1]]
-            r.full = {int(k): int(v) for k, v in enumerate(full[i]) if v}
-            r.pref = {int(k): int(v) for k, v in enumerate(pref[i]) if v}
-            r.rept_hist = {int(k): int(v) for k, v in enumerate(rept[i]) if v}
-            r.rept = int(rept[i].sum())
-            r.call = calls[i]
-            r.grid = dump[goff[i]:goff[i] + calls[i]["n_pairs"]] if dump is not None and calls[i]["status"] == 0 else None
-            r.joint = joint[i] if joint is not None and calls[i]["status"] == 0 else None
-            r.P_h1, r.P_h2 = marg[i, 0], marg[i, 1]
-            out.append(r)
-        return out
-
-    def _grid(self, units, hs, full, pref, rept, want_grid, dense=False):
-        """One grid call for the batch.  want_grid: also the joint distribution -- sparse (triples + total per
-        unit, tredgpu_likelihood_grid_joint) unless dense=True asks for the full dump of every pair."""
-        up = np.zeros(len(units), _lib.UNIT_DTYPE)
-        gl, tl = [], []
-        for i, u in enumerate(units):
-            t = u.tred
-            up[i] = (len(t.repeat), u.readlen, u.ploidy, u.maxinsert, int(u.fullsearch), u.ref_len, u.minpe,
-                     int(t.cutoff_risk), int(t.is_expansion), int(t.is_recessive), len(gl), len(u.global_lens),
-                     len(tl), len(u.target_lens), u.depth / 2)
-            gl += u.global_lens
-            tl += u.target_lens
-        hist = (up, hs, full, pref, rept, np.asarray(gl, np.int32), np.asarray(tl, np.int32))
-        calls, marg, joint, _ = self._grid_arrays(*hist, joint=want_grid and not dense)
-        dump, goff = self._dense_dump(*hist, calls) if want_grid and dense else (None, None)
-        return calls, marg, dump, goff, joint
+        """SW + tagging -> histograms -> likelihood grid for a batch of units (a list of Unit, or a PackedUnits); returns
+        [UnitResult], with the histograms.  want_grid=False: no joint distribution."""
+        b = _batch(units)
+        r = self._genotype_packed_stepwise(b, joint=want_grid, refuse_invalid=True)
+        return [r.unit(i) for i in range(b.n_units)]
 
     def grid_from_counts(self, unit, full, pref, rept):
         """Likelihood grid of one unit from explicit histograms {units: count} (IntegratedCaller.call)."""
-        keys = list(full) + list(pref) + [unit.max_units]
-        hs = max(keys) + 2
-        f = np.zeros((1, hs), np.int32)
-        p = np.zeros((1, hs), np.int32)
-        r = np.zeros((1, hs), np.int32)
-        for k, v in full.items():
-            f[0, k] = v
-        for k, v in pref.items():
-            p[0, k] = v
+        b = PackedUnits.from_units([unit])
+        hs = max(list(full) + list(pref) + [unit.max_units]) + 2
+        f, p, r = (np.zeros((1, hs), np.int32) for _ in range(3))
+        for row, counts in ((f, full), (p, pref)):
+            for k, v in counts.items():
+                row[0, k] = v
         r[0, 0] = rept
-        calls, marg, dump, goff, _ = self._grid([unit], hs, f, p, r, True, dense=True)
+        hist = (b.params, hs, f, p, r, b.global_lens, b.target_lens)
+        calls, marg, _, _ = self._grid_arrays(*hist, joint=False)
+        dump, goff = self._dense_dump(*hist, calls)
         res = UnitResult()
-        res.tags = res.hs = res.scores = None
+        res.tags = res.hs = res.scores = res.joint = None
         res.full, res.pref, res.rept_hist, res.rept = dict(full), dict(pref), {}, rept
         res.call = calls[0]
         res.grid = dump[goff[0]:goff[0] + calls[0]["n_pairs"]] if calls[0]["status"] == 0 else None
-        res.joint = None
         res.P_h1, res.P_h2 = marg[0, 0], marg[0, 1]
         return res
+
+
+def _batch(units):
+    return units if isinstance(units, PackedUnits) else PackedUnits.from_units(units)
+
+
+def _refuse_invalid(tag):
+    if (tag == _lib.TAG_INVALID).any():
+        raise _lib.TredGpuError("a read exceeds TREDGPU_MAX_READ_LEN")
+
+
+def _gather_reads(packed, read_off, read_len, reads):
+    """(packed, read_off, read_len) of the reads `reads` (indices) of a packed pool: their words, gathered by index."""
+    lo = read_off[reads]
+    size = read_off[reads + 1] - lo
+    off = np.zeros(len(reads) + 1, np.int64)
+    np.cumsum(size, out=off[1:])
+    return (np.ascontiguousarray(packed[_ranges(lo, size, force=True)], np.uint32), off,
+            np.ascontiguousarray(read_len[reads], np.int32))

@@ -251,12 +251,11 @@ def _genotype(engine, picks, o):
         br = engine.genotype_packed(batch, dense=True) if o["log"] == "DEBUG" else engine.genotype_packed(batch)
         br.repeatpairs = kw["repeatpairs"]
         if o["alignments"] or o["consensus"]:
-            units = _alignment_units(sub, o["clip"])
-            winners = engine.winners(units)                       # classify with the dump and the CIGAR call: once for both
+            winners = engine.winners(batch)                       # classify with the dump and the CIGAR call: once for both
             if o["alignments"]:
-                br.alignments = engine.alignments(units, winners=winners)
+                br.alignments = engine.alignments(batch, winners=winners)
             if o["consensus"]:
-                br.consensus = engine.consensus(units, _called_alleles(br), winners=winners)
+                br.consensus = engine.consensus(batch, _called_alleles(br), winners=winners)
         i = 0
         for si, _, ks in sub:
             if ks:
@@ -277,17 +276,6 @@ def _genotype(engine, picks, o):
                     except TredGpuError as e1:
                         logger.error("Exception on `%s` %s (%s)", s.path, s.names[k], e1)
     return out
-
-
-def _alignment_units(sub, clip):
-    """The units of _genotype's picks, in the batch's order, as Engine.alignments takes them: their reads as text."""
-    from .engine import Unit
-    units = []
-    for _, s, ks in sub:
-        for k in ks:
-            a, b = s.reads_of(k)
-            units.append(Unit(s.loci[k], s.readlen, [s.sequence(i) for i in range(a, b)], s.depth[k], s.ploidy[k], (), (), clip=clip))
-    return units
 
 
 def _called_alleles(br):
