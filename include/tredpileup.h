@@ -7,7 +7,10 @@
  * letter each read shows there, whether it skips the column, and what it inserts before it.  That table is what a
  * consensus of the tract, and so an interruption of it (CAA in HTT, AGG in FMR1), is read from.
  *
- * Opt-in: nothing else in libtredgpu calls it (Engine.consensus, tred.py --consensus).
+ * tredpileup_pileup_anchored does the same for an allele LONGER than its reads, which no read spans: a read that begins in
+ * one flank and ends inside the tract is laid on the allele's template from the side of that flank.
+ *
+ * Opt-in: nothing else in libtredgpu calls them (Engine.consensus, tred.py --consensus / --consensus-partial).
  */
 #ifndef TREDPILEUP_H
 #define TREDPILEUP_H
@@ -25,6 +28,10 @@ extern "C" {
                                       > cap; an operation other than M / I / D or of length 0; M + D lengths that are not
                                       ref_end - ref_begin + 1 or M + I lengths that are not read_end - read_begin + 1; a
                                       (ladder, units) other than that of the group's first accepted item */
+
+#define TREDGPU_PILEUP_ANCHOR_WHOLE 0  /* item_anchor of tredpileup_pileup_anchored: the item spans the group's allele */
+#define TREDGPU_PILEUP_ANCHOR_BEGIN 1  /* it lies at the begin of its OWN template (a read tagged PREF) */
+#define TREDGPU_PILEUP_ANCHOR_END 2    /* ... at the end of its own template (POST) */
 
 #define TREDGPU_PILEUP_CHANNELS 8
 #define TREDGPU_PILEUP_MAX_STRIDE 65536
@@ -65,7 +72,39 @@ int tredpileup_pileup(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* pr
                       const int32_t* read_len, int64_t n_items, const int32_t* item_ladder, const int32_t* item_template,
                       const int16_t* fields, const uint32_t* ops, int32_t cap, const int32_t* n_ops, const int32_t* item_group,
                       int32_t n_groups, int32_t stride, int32_t* out_counts, int32_t* out_status);
-/* calls of tredpileup_pileup on this context since tredpileup_reset_timing and the summed device time of their kernels
+/*
+ * The same pileup with the shape of every group GIVEN and an anchor per item, for alleles longer than the reads.  The
+ * arguments of tredpileup_pileup, and
+ *   item_anchor[n_items]   TREDGPU_PILEUP_ANCHOR_*
+ *   group_ladder[n_groups], group_units[n_groups]   the group's ladder and its allele a >= 1, which MAY exceed the
+ *                      ladder's max_units: the group's template is prefix + repeat * a + suffix, of T_a columns
+ *   stride             at least the largest GROUP template length + 1, at most TREDGPU_PILEUP_MAX_STRIDE; the ladders' own
+ *                      templates do not bound it
+ * With P, p, S the lengths of prefix, repeat and suffix, an item of template index tpl has h = tpl / 2 + 1 units, strand
+ * tpl & 1 and T_h = P + p * h + S columns of its own.  Its forward column and forward slot on its OWN template are what
+ * tredpileup_pileup counts: c or T_h - 1 - c, slot r or T_h - r.
+ * Refused with TREDGPU_PILEUP_BAD_ITEM, besides everything tredpileup_pileup refuses (those checks come first, TOO_LONG
+ * among them): item_ladder other than group_ladder[group]; a ladder with max_units <= 0 (a plain reference has no tract to
+ * anchor on); an anchor outside 0..2; h > a; anchor WHOLE with h != a.  Every refusal is the item's own: the group has its
+ * shape whether or not an item is accepted.
+ * Counting.  h == a: the item counts whole, as in tredpileup_pileup, whatever its anchor.  Otherwise its forward side is
+ * LEFT when (anchor == BEGIN) != (strand == 1), else RIGHT -- tags are decided on the template aligned to, so a PREF read
+ * on a reverse-complement template sits at the suffix end of the forward one.
+ *   LEFT   keeps forward columns f < P + p * h and forward slots s < P + p * h (slot 0 included), where they are
+ *   RIGHT  keeps forward columns f >= P and forward slots P < s <= T_h, moved up by (a - h) * p
+ * What the item shows of the other flank -- columns that would lie inside the group's tract -- is cut, the slot at the
+ * cut is dropped, and an M, D or I operation across the cut counts on the kept side only.
+ * Returns as tredpileup_pileup; -2 (nothing written) also for a NULL array, a group_ladder out of range, a group_units
+ * below 1 and a stride below the largest group template + 1.  Host memory only; the same state, stream and staging.
+ */
+int tredpileup_pileup_anchored(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat,
+                               const char* const* suffix, const int32_t* max_units, const uint32_t* packed,
+                               const int64_t* read_off, const int32_t* read_len, int64_t n_items, const int32_t* item_ladder,
+                               const int32_t* item_template, const int16_t* fields, const uint32_t* ops, int32_t cap,
+                               const int32_t* n_ops, const int32_t* item_group, const int32_t* item_anchor, int32_t n_groups,
+                               const int32_t* group_ladder, const int32_t* group_units, int32_t stride, int32_t* out_counts,
+                               int32_t* out_status);
+/* calls of tredpileup_pileup and tredpileup_pileup_anchored on this context since tredpileup_reset_timing and the summed device time of their kernels
    (HIP events, one pair around the launches of a call) */
 int tredpileup_get_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms);
 int tredpileup_reset_timing(tredgpu_ctx* ctx);

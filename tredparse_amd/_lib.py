@@ -69,9 +69,10 @@ SECOND_EXPORTS = ("tredsecond_sw_second", "tredsecond_get_timing", "tredsecond_r
 SECOND_OK, SECOND_TOO_LONG, SECOND_BAD_ITEM = 0, 4, 5
 
 # the pileup's symbols (include/tredpileup.h)
-PILEUP_EXPORTS = ("tredpileup_pileup", "tredpileup_get_timing", "tredpileup_reset_timing", "tredpileup_release",
-                  "tredpileup_last_error")
+PILEUP_EXPORTS = ("tredpileup_pileup", "tredpileup_pileup_anchored", "tredpileup_get_timing", "tredpileup_reset_timing",
+                  "tredpileup_release", "tredpileup_last_error")
 PILEUP_OK, PILEUP_TOO_LONG, PILEUP_BAD_ITEM = 0, 4, 5
+PILEUP_ANCHOR_WHOLE, PILEUP_ANCHOR_BEGIN, PILEUP_ANCHOR_END = 0, 1, 2   # item_anchor of pileup_anchored: FULL, PREF, POST
 PILEUP_CHANNELS = 8             # A C G T N, deleted, insertions before the column, their summed length
 
 # every symbol include/tredgpu.h declares (tests check the .so exports them all)
@@ -131,6 +132,8 @@ def load():
                                          vp, vp, vp, vp, i64, vp, vp, vp, C.POINTER(SwParams), vp, vp]
     lib.tredpileup_pileup.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                       vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp]
+    lib.tredpileup_pileup_anchored.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                               vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
     for prefix, get_timing, reset_timing, _, last_error in SIDE_UNITS:
         getattr(lib, get_timing).argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
         getattr(lib, reset_timing).argtypes = [vp]
@@ -635,6 +638,22 @@ class Context:
                                         _ptr(item_ladder), _ptr(item_template), _ptr(fields), _ptr(ops), cap, _ptr(n_ops),
                                         _ptr(item_group), n_groups, stride, _ptr(out_counts), _ptr(out_status))
         self._chk_side(rc, "tredpileup_pileup failed ({})".format(rc), self.lib.tredpileup_last_error)
+
+    def pileup_anchored(self, packed, read_off, read_len, n_items, item_ladder, item_template, fields, ops, cap, n_ops,
+                        item_group, item_anchor, n_groups, group_ladder, group_units, stride, out_counts, out_status,
+                        ladders=None):
+        """tredpileup_pileup_anchored (include/tredpileup.h): pileup with the shape of every group given -- group_ladder,
+        group_units (int32 [n_groups]): the allele a >= 1 of the group, which may lie beyond the ladder -- and an anchor per
+        item (item_anchor int32 [n], PILEUP_ANCHOR_*): an item of h < a units keeps the flank it is anchored in and the
+        tract next to it, moved to where they lie on the group's template.  stride: at least the longest GROUP template
+        + 1.  Everything else as pileup takes it."""
+        table = _ladder_args(list(self.ladders if ladders is None else ladders))
+        rc = self.lib.tredpileup_pileup_anchored(self.h, *table, _ptr(packed), _ptr(read_off), _ptr(read_len), n_items,
+                                                 _ptr(item_ladder), _ptr(item_template), _ptr(fields), _ptr(ops), cap,
+                                                 _ptr(n_ops), _ptr(item_group), _ptr(item_anchor), n_groups,
+                                                 _ptr(group_ladder), _ptr(group_units), stride, _ptr(out_counts),
+                                                 _ptr(out_status))
+        self._chk_side(rc, "tredpileup_pileup_anchored failed ({})".format(rc), self.lib.tredpileup_last_error)
 
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")

@@ -1,5 +1,6 @@
 """What Engine.consensus reports of one allele: the pileup table of the reads that span it (Context.pileup,
-include/tredpileup.h) read column by column.  Plain numpy, no GPU: the table is the kernel's, the rules are here."""
+include/tredpileup.h) -- with partial=True also of the reads anchored in one flank (Context.pileup_anchored) -- read
+column by column.  Plain numpy, no GPU: the table is the kernel's, the rules are here."""
 import numpy as np
 
 LETTERS = "ACGTN-"           # the table's channels 0-5; 6: insertions before the column, 7: their summed length
@@ -19,12 +20,17 @@ class AlleleConsensus(object):
       interruptions   the tract columns with depth >= 2 whose consensus is not T[c] and holds more than half the depth:
                       {"unit" (1-based), "offset" (in the unit), "ref", "alt", "support", "depth"}
       insertions      {"before": column, "reads", "bases"} for every slot with an insertion
+      partial         the PREF / POST reads laid on the allele from the side of their flank (Engine.consensus(partial=True);
+                      0 otherwise).  Their columns are in counts with those of the FULL reads
+      ambiguous, beyond   the PREF / POST reads of the unit laid nowhere: short enough to fit any allele asked for, and
+                      longer than the longest.  Non-zero only on the unit's longest allele
     """
-    __slots__ = ("h", "reads", "counts", "depth", "consensus", "interruptions", "insertions")
+    __slots__ = ("h", "reads", "counts", "depth", "consensus", "interruptions", "insertions", "partial", "ambiguous", "beyond")
 
-    def __init__(self, h, reads, counts, template, prefix_len, period):
+    def __init__(self, h, reads, counts, template, prefix_len, period, partial=0, ambiguous=0, beyond=0):
         T = len(template)
         self.h, self.reads = int(h), int(reads)
+        self.partial, self.ambiguous, self.beyond = int(partial), int(ambiguous), int(beyond)
         self.counts = np.ascontiguousarray(counts[:T + 1], np.int32)
         six = self.counts[:T, :6].astype(np.int64)
         self.depth = six.sum(axis=1)
@@ -44,7 +50,10 @@ class AlleleConsensus(object):
         self.insertions = [{"before": c, "reads": int(self.counts[c, 6]), "bases": int(self.counts[c, 7])}
                            for c in np.nonzero(self.counts[:, 6] > 0)[0].tolist()]
 
-    def to_dict(self):
-        """What tred.py --consensus writes of the allele."""
-        return {"h": self.h, "reads": self.reads, "consensus": self.consensus, "depth": [int(v) for v in self.depth],
-                "interruptions": self.interruptions, "insertions": self.insertions}
+    def to_dict(self, partial=False):
+        """What tred.py --consensus writes of the allele; partial: and what --consensus-partial adds."""
+        d = {"h": self.h, "reads": self.reads, "consensus": self.consensus, "depth": [int(v) for v in self.depth],
+             "interruptions": self.interruptions, "insertions": self.insertions}
+        if partial:
+            d.update(partial=self.partial, ambiguous=self.ambiguous, beyond=self.beyond)
+        return d

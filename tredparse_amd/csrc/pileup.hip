@@ -19,6 +19,12 @@
 //     -- every cell of out_counts has exactly one owner, there is no global atomic, and the result is exact and order-free.
 //     The workgroup of a group's tile 0 also refuses the accepted items whose (ladder, units) is not the group's.
 //   * counters are 32-bit: a group may hold any number of items a call can carry (n_items < 2^31).
+//
+// tredpileup_pileup_anchored is the same call with the group's shape GIVEN (group_ladder, group_units = a, which may lie
+// beyond the ladder) and an anchor per item: validate_anchored_kernel adds the refusals that compare an item with its
+// group, so pileup_anchored_kernel needs no first-item search, and an item of h < a units is counted by the SAME walker
+// (count_item) with a window of its forward columns and slots and a shift -- the flank it is anchored in and the tract
+// next to it land where they lie on the group's template, what it shows of the other flank is cut.
 #include <climits>
 #include <cstring>
 
@@ -54,6 +60,7 @@ struct PileArgs {
     int32_t* pre;              // [n_items]: the status of validate_kernel
     int32_t* out_counts;       // [n_groups][stride][CH]
     int32_t* out_status;
+    const int32_t *item_anchor, *group_ladder, *group_units;     // the anchored entry's; NULL otherwise
     const uint8_t* letters;    // fill_table's other fields, which no kernel of this unit reads
     int32_t match, mismatch, gap_open, gap_extend;
 };
@@ -93,15 +100,44 @@ __global__ __launch_bounds__(256) void validate_kernel(PileArgs a) {
     a.out_status[item] = status;
 }
 
-// One accepted item of the group into the tile [tile0, tile0 + TILE) of cnt ([CH][TILE]); T: the template's length.
-// The whole wavefront is here with the same item.
-__device__ __forceinline__ void count_item(const PileArgs& a, int64_t item, int strand, int T, int tile0, int* cnt) {
+// validate, then what the anchored entry asks of an item against its group (whose ladder and units the host has checked):
+// the group's ladder, a ladder with a tract, an anchor of 0..2, no more units than the group, and all of them when WHOLE
+__device__ int validate_anchored(const PileArgs& a, int64_t item) {
+    const int status = validate(a, item);
+    if (status != TREDGPU_PILEUP_OK) return status;
+    const int g = a.item_group[item], lad = a.item_ladder[item];   // both in range: validate has looked
+    if (lad != a.group_ladder[g] || a.ladders[lad].max_units <= 0) return TREDGPU_PILEUP_BAD_ITEM;
+    const int anchor = a.item_anchor[item], h = a.item_template[item] / 2 + 1, units = a.group_units[g];
+    if (anchor < TREDGPU_PILEUP_ANCHOR_WHOLE || anchor > TREDGPU_PILEUP_ANCHOR_END) return TREDGPU_PILEUP_BAD_ITEM;
+    if (h > units || (anchor == TREDGPU_PILEUP_ANCHOR_WHOLE && h != units)) return TREDGPU_PILEUP_BAD_ITEM;
+    return TREDGPU_PILEUP_OK;
+}
+
+__global__ __launch_bounds__(256) void validate_anchored_kernel(PileArgs a) {
+    const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= a.n_items) return;
+    const int status = validate_anchored(a, item);
+    a.pre[item] = status;
+    a.out_status[item] = status;
+}
+
+// The forward columns [col_lo, col_hi) and slots [slot_lo, slot_hi) of an item's OWN template that count, and what is added
+// to them on the way to the group's table.  whole(T): all of a template of T columns, where it lies.
+struct Window { int col_lo, col_hi, slot_lo, slot_hi, shift; };
+__device__ __forceinline__ Window whole(int T) { return {0, T, 0, T + 1, 0}; }
+
+// One accepted item into the tile [tile0, tile0 + TILE) of cnt ([CH][TILE]); T: the length of the item's own template, w:
+// what of it counts.  The whole wavefront is here with the same item.
+__device__ __forceinline__ void count_item(const PileArgs& a, int64_t item, int strand, int T, const Window w, int tile0, int* cnt) {
     const int lane = threadIdx.x & 63;
     const int16_t* fl = a.fields + (size_t)item * 5;
     const int ref_begin = fl[1], ref_end = fl[2];
-    // the forward columns and slots the item can touch: its columns and the slot behind the last
-    const int lo = strand ? T - 1 - ref_end : ref_begin, hi = strand ? T - ref_begin : ref_end + 1;
-    if (hi < tile0 || lo >= tile0 + TILE) return;
+    // the forward columns and slots the item can touch: its columns and the slot behind the last, as far as they count
+    const int lo = max(strand ? T - 1 - ref_end : ref_begin, min(w.col_lo, w.slot_lo));
+    const int hi = min(strand ? T - ref_begin : ref_end + 1, max(w.col_hi, w.slot_hi) - 1);
+    if (hi + w.shift < tile0 || lo + w.shift >= tile0 + TILE) return;
+    // the tile in the item's own forward columns, cut to the window
+    const int org = tile0 - w.shift, wlo = max(w.col_lo, org), whi = min(w.col_hi, org + TILE);
     const uint32_t* rec = a.packed + a.read_off[item];
     const int nb = (a.read_len[item] + 15) >> 4;
     const uint32_t* ops = a.ops + (size_t)item * a.cap;
@@ -110,20 +146,20 @@ __device__ __forceinline__ void count_item(const PileArgs& a, int64_t item, int 
     for (int j = 0; j < n; ++j) {
         const int op = (int)(ops[j] & 15u), len = (int)(ops[j] >> 4);
         if (op == 1) {                                             // an insertion before column r of the item's strand
-            const int slot = (strand ? T - r : r) - tile0;
-            if (lane == 0 && slot >= 0 && slot < TILE) {
+            const int fwd = strand ? T - r : r, slot = fwd - org;
+            if (lane == 0 && fwd >= w.slot_lo && fwd < w.slot_hi && slot >= 0 && slot < TILE) {
                 atomicAdd(&cnt[6 * TILE + slot], 1);
                 atomicAdd(&cnt[7 * TILE + slot], len);
             }
             q += len;
             continue;
         }
-        // k in [klo, khi): the steps of the operation whose forward column r + k, or T - 1 - r - k, lies in the tile
+        // k in [klo, khi): the steps of the operation whose forward column r + k, or T - 1 - r - k, lies in [wlo, whi)
         const int base = strand ? T - 1 - r : r;
-        const int klo = strand ? max(0, base - tile0 - TILE + 1) : max(0, tile0 - base);
-        const int khi = strand ? min(len, base - tile0 + 1) : min(len, tile0 + TILE - base);
+        const int klo = strand ? max(0, base - whi + 1) : max(0, wlo - base);
+        const int khi = strand ? min(len, base - wlo + 1) : min(len, whi - base);
         for (int k = klo + lane; k < khi; k += 64) {
-            const int col = (strand ? base - k : base + k) - tile0;
+            const int col = (strand ? base - k : base + k) - org;
             int ch = 5;
             if (op == 0) {
                 const int code = read_code(rec, nb, q + k);
@@ -136,6 +172,16 @@ __device__ __forceinline__ void count_item(const PileArgs& a, int64_t item, int 
     }
 }
 
+// a work unit's counters: zeroed by the whole workgroup, and stored once with plain vector stores, zeros included
+__device__ __forceinline__ void zero_tile(int* cnt) {
+    for (int k = threadIdx.x; k < CH * TILE; k += THREADS) cnt[k] = 0;
+}
+__device__ __forceinline__ void store_tile(const PileArgs& a, int g, int tile0, const int* cnt) {
+    int32_t* out = a.out_counts + ((size_t)g * a.stride + tile0) * CH;
+    const int cols = min(TILE, a.stride - tile0);
+    for (int k = threadIdx.x; k < cols * CH; k += THREADS) out[k] = cnt[(k % CH) * TILE + k / CH];
+}
+
 __global__ __launch_bounds__(THREADS) void pileup_kernel(PileArgs a) {
     __shared__ int cnt[CH * TILE];
     __shared__ int first;
@@ -145,7 +191,7 @@ __global__ __launch_bounds__(THREADS) void pileup_kernel(PileArgs a) {
         const int g = (int)(w / a.ntile), tile0 = (int)(w % a.ntile) * TILE;
         const int64_t lo = a.goff[g], hi = a.goff[g + 1];
         __syncthreads();                                           // the unit before has stored its tile
-        for (int k = threadIdx.x; k < CH * TILE; k += THREADS) cnt[k] = 0;
+        zero_tile(cnt);
         if (threadIdx.x == 0) first = INT_MAX;
         __syncthreads();
         for (int64_t k = lo + threadIdx.x; k < hi; k += THREADS)
@@ -165,28 +211,56 @@ __global__ __launch_bounds__(THREADS) void pileup_kernel(PileArgs a) {
                     if (tile0 == 0 && lane == 0) a.out_status[item] = TREDGPU_PILEUP_BAD_ITEM;
                     continue;
                 }
-                if (tile0 <= T) count_item(a, item, d.max_units > 0 ? (tpl & 1) : 0, T, tile0, cnt);
+                if (tile0 <= T) count_item(a, item, d.max_units > 0 ? (tpl & 1) : 0, T, whole(T), tile0, cnt);
             }
         }
         __syncthreads();
-        int32_t* out = a.out_counts + ((size_t)g * a.stride + tile0) * CH;
-        const int cols = min(TILE, a.stride - tile0);
-        for (int k = threadIdx.x; k < cols * CH; k += THREADS) out[k] = cnt[(k % CH) * TILE + k / CH];
+        store_tile(a, g, tile0, cnt);
+    }
+}
+
+// The same work units with the group's shape given: every accepted item of the list belongs to the group (validate_anchored),
+// so there is nothing to search or to refuse here.  An item of the group's own units counts whole; a shorter one keeps the
+// flank it is anchored in and the tract next to it -- LEFT of the forward template for BEGIN on a forward and END on a
+// reverse-complement template, RIGHT otherwise, and RIGHT is shifted by the units the group has more.
+__global__ __launch_bounds__(THREADS) void pileup_anchored_kernel(PileArgs a) {
+    __shared__ int cnt[CH * TILE];
+    const int wave = threadIdx.x >> 6;
+    const int64_t n_work = (int64_t)a.n_groups * a.ntile;
+    for (int64_t w = blockIdx.x; w < n_work; w += gridDim.x) {
+        const int g = (int)(w / a.ntile), tile0 = (int)(w % a.ntile) * TILE;
+        const int64_t lo = a.goff[g], hi = a.goff[g + 1];
+        __syncthreads();                                           // the unit before has stored its tile
+        zero_tile(cnt);
+        __syncthreads();
+        const LadderRecord d = a.ladders[a.group_ladder[g]];       // (in range: the host has looked)
+        const int units = a.group_units[g], P = d.alen[0], p = d.period;
+        if (tile0 <= P + p * units + d.blen[0])
+            for (int64_t k = lo + wave; k < hi; k += WAVES) {
+                const int item = a.order[k];
+                if (a.pre[item] != TREDGPU_PILEUP_OK) continue;
+                const int tpl = a.item_template[item], h = tpl / 2 + 1, strand = tpl & 1, T = P + p * h + d.blen[0];
+                Window win = whole(T);
+                if (h != units) {
+                    const bool left = (a.item_anchor[item] == TREDGPU_PILEUP_ANCHOR_BEGIN) != (strand == 1);
+                    win = left ? Window{0, P + p * h, 0, P + p * h, 0} : Window{P, T, P + 1, T + 1, (units - h) * p};
+                }
+                count_item(a, item, strand, T, win, tile0, cnt);
+            }
+        __syncthreads();
+        store_tile(a, g, tile0, cnt);
     }
 }
 
 struct State : StateBase {};
 Registry<State> g_states;
 
-}  // namespace
-
-extern "C" {
-
-int tredpileup_pileup(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat,
-                      const char* const* suffix, const int32_t* max_units, const uint32_t* packed, const int64_t* read_off,
-                      const int32_t* read_len, int64_t n_items, const int32_t* item_ladder, const int32_t* item_template,
-                      const int16_t* fields, const uint32_t* ops, int32_t cap, const int32_t* n_ops, const int32_t* item_group,
-                      int32_t n_groups, int32_t stride, int32_t* out_counts, int32_t* out_status) {
+// Both entries.  anchor / group_ladder / group_units: the anchored entry's three arrays, all NULL for tredpileup_pileup.
+int run(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat, const char* const* suffix,
+        const int32_t* max_units, const uint32_t* packed, const int64_t* read_off, const int32_t* read_len, int64_t n_items,
+        const int32_t* item_ladder, const int32_t* item_template, const int16_t* fields, const uint32_t* ops, int32_t cap,
+        const int32_t* n_ops, const int32_t* item_group, int32_t n_groups, int32_t stride, int32_t* out_counts,
+        int32_t* out_status, bool anchored, const int32_t* item_anchor, const int32_t* group_ladder, const int32_t* group_units) {
     std::string& err = g_pileup_error;
     err.clear();
     const Table t{n_ladders, prefix, repeat, suffix, max_units};
@@ -195,12 +269,21 @@ int tredpileup_pileup(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* pr
                           {packed, read_off, read_len, item_ladder, item_template, fields, ops, n_ops, item_group, out_status});
     if (rc) return rc;
     if (n_groups < 0 || (n_groups > 0 && !out_counts)) return fail(err, -2, "n_groups must not be negative, nor out_counts NULL");
+    if (anchored && ((n_items > 0 && !item_anchor) || (n_groups > 0 && (!group_ladder || !group_units))))
+        return fail(err, -2, "NULL array argument");
     size_t longest = 0;
     for (int i = 0; i < n_ladders; ++i) {
         if (!prefix[i] || !repeat[i] || !suffix[i]) return fail(err, -2, "ladder %d: NULL sequence", i);
+        if (anchored) continue;
         const size_t T = max_units[i] > 0 ? strlen(prefix[i]) + strlen(suffix[i]) + strlen(repeat[i]) * (size_t)max_units[i]
                                           : strlen(prefix[i]);
         longest = std::max(longest, std::min<size_t>(T, TREDGPU_MAX_LONG_TEMPLATE_LEN));
+    }
+    for (int g = 0; anchored && g < n_groups; ++g) {               // the shape is the group's own, wherever the ladder ends
+        const int lad = group_ladder[g];
+        if (lad < 0 || lad >= n_ladders) return fail(err, -2, "group %d: ladder %d out of range", g, lad);
+        if (group_units[g] < 1) return fail(err, -2, "group %d: units %d must be at least 1", g, group_units[g]);
+        longest = std::max(longest, strlen(prefix[lad]) + strlen(suffix[lad]) + strlen(repeat[lad]) * (size_t)group_units[g]);
     }
     if (stride <= 0 || (size_t)stride < longest + 1 || stride > TREDGPU_PILEUP_MAX_STRIDE)
         return fail(err, -2, "stride %d must be at least the largest template length + 1 = %zu and at most %d", stride,
@@ -224,21 +307,56 @@ int tredpileup_pileup(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* pr
 
     PileArgs a{};
     fill_table(a, s, any_scoring);
-    const std::vector<Array> arrays = {
+    std::vector<Array> arrays = {
         arr_in(a.packed, packed, (size_t)read_off[n]), arr_in(a.read_off, read_off, n + 1), arr_in(a.read_len, read_len, n),
         arr_in(a.item_ladder, item_ladder, n), arr_in(a.item_template, item_template, n), arr_in(a.fields, fields, n * 5),
         arr_in(a.ops, ops, n * (size_t)cap), arr_in(a.n_ops, n_ops, n), arr_in(a.item_group, item_group, n),
         arr_in(a.order, order.data(), order.size()), arr_in(a.goff, goff.data(), goff.size()), arr_scratch(a.pre, n),
         arr_out(a.out_counts, out_counts, cells), arr_out(a.out_status, out_status, n)};
+    if (anchored) {
+        arrays.push_back(arr_in(a.item_anchor, item_anchor, n));
+        arrays.push_back(arr_in(a.group_ladder, group_ladder, (size_t)n_groups));
+        arrays.push_back(arr_in(a.group_units, group_units, (size_t)n_groups));
+    }
     if ((rc = stage(err, s, st, arrays))) return rc;
     a.n_items = n_items; a.cap = cap; a.n_groups = n_groups; a.stride = stride; a.ntile = (stride + TILE - 1) / TILE;
 
     if ((rc = timed_begin(err, s, st))) return rc;
-    hipLaunchKernelGGL(validate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-    const int64_t n_work = (int64_t)n_groups * a.ntile;
-    hipLaunchKernelGGL(pileup_kernel, dim3((unsigned)std::min<int64_t>(n_work, MAX_BLOCKS)), dim3(THREADS), 0, st, a);
+    const dim3 per_item((unsigned)((n + 255) / 256)), per_tile((unsigned)std::min<int64_t>((int64_t)n_groups * a.ntile, MAX_BLOCKS));
+    if (anchored) {
+        hipLaunchKernelGGL(validate_anchored_kernel, per_item, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(pileup_anchored_kernel, per_tile, dim3(THREADS), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(validate_kernel, per_item, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(pileup_kernel, per_tile, dim3(THREADS), 0, st, a);
+    }
     if ((rc = timed_end(err, s, st))) return rc;
     return read_back(err, s, st, arrays);                          // (order and goff are read by their copies until the stream is drained)
+}
+
+}  // namespace
+
+extern "C" {
+
+int tredpileup_pileup(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat,
+                      const char* const* suffix, const int32_t* max_units, const uint32_t* packed, const int64_t* read_off,
+                      const int32_t* read_len, int64_t n_items, const int32_t* item_ladder, const int32_t* item_template,
+                      const int16_t* fields, const uint32_t* ops, int32_t cap, const int32_t* n_ops, const int32_t* item_group,
+                      int32_t n_groups, int32_t stride, int32_t* out_counts, int32_t* out_status) {
+    return run(ctx, n_ladders, prefix, repeat, suffix, max_units, packed, read_off, read_len, n_items, item_ladder, item_template,
+               fields, ops, cap, n_ops, item_group, n_groups, stride, out_counts, out_status, false, nullptr, nullptr, nullptr);
+}
+
+int tredpileup_pileup_anchored(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat,
+                               const char* const* suffix, const int32_t* max_units, const uint32_t* packed,
+                               const int64_t* read_off, const int32_t* read_len, int64_t n_items, const int32_t* item_ladder,
+                               const int32_t* item_template, const int16_t* fields, const uint32_t* ops, int32_t cap,
+                               const int32_t* n_ops, const int32_t* item_group, const int32_t* item_anchor, int32_t n_groups,
+                               const int32_t* group_ladder, const int32_t* group_units, int32_t stride, int32_t* out_counts,
+                               int32_t* out_status) {
+    return run(ctx, n_ladders, prefix, repeat, suffix, max_units, packed, read_off, read_len, n_items, item_ladder, item_template,
+               fields, ops, cap, n_ops, item_group, n_groups, stride, out_counts, out_status, true, item_anchor, group_ladder,
+               group_units);
 }
 
 int tredpileup_get_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms) { return timing(g_pileup_error, g_states, ctx, launches, total_ms, false); }

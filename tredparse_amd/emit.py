@@ -84,7 +84,7 @@ class Emitter(object):
             if o["consensus"]:
                 from .tred import consensus_text
                 with open(result["samplekey"] + ".consensus.json", "w") as fp:
-                    fp.write(consensus_text(scan, result["tredCalls"], {k: r for (_, k), r in res.items()}))
+                    fp.write(consensus_text(scan, result["tredCalls"], {k: r for (_, k), r in res.items()}, partial=o["consensus_partial"]))
         if self.on_sample is not None:
             calls = result["tredCalls"]
             self.on_sample({"samplekey": result["samplekey"], "names": scan.names,

@@ -592,16 +592,24 @@ class Engine(object):
         return out
 
     # ---- what is in the tract of an allele --------------------------------------------------------------
-    def consensus(self, units, alleles, winners=None):
+    def consensus(self, units, alleles, winners=None, partial=False):
         """Per unit: {a: consensus.AlleleConsensus} for every a >= 1 of alleles[unit] (repeat units): the reads of the
         unit tagged FULL with h == a, laid on prefix + repeat * a + suffix by the alignments of self.winners (winners:
         what it returned, when the caller already has it) and counted column by column in ONE pileup call for all units
         and alleles -- one group per (unit, a).  Only FULL reads count: a partial (PREF / POST) or repeat-only read is
         tagged with the longest template it fits, not with an allele, so it cannot be placed on an allele's template.
         An allele no FULL read was counted for -- an expansion longer than the reads, say -- comes back with reads = 0,
-        its template in lower case and empty lists."""
+        its template in lower case and empty lists.
+
+        partial=True lays the PREF / POST reads down too, in ONE pileup_anchored call with the FULL reads: of a unit whose
+        longest allele asked for is a_k and next longest a_prev (0 when there is none), a partial read with
+        a_prev < h <= a_k can only come from a_k and is laid on it from the side of its flank (AlleleConsensus.partial);
+        one with h <= a_prev fits any allele asked for and is counted as `ambiguous`, one with h > a_k as `beyond`, both on
+        a_k and laid nowhere.  REPT and HANG reads are never placed."""
         from .consensus import AlleleConsensus
         w = self.winners(units) if winners is None else winners
+        if partial:
+            return self._consensus_partial(w, alleles)
         b = w.batch
         group_of, groups = {}, []
         for g, want in enumerate(alleles):
@@ -640,6 +648,69 @@ class Engine(object):
             if n_reads[k]:
                 table[:] = counts[k, :len(T) + 1]          # (a group with reads has a template of the ladder: it fits the stride)
             out[g][a] = AlleleConsensus(a, n_reads[k], table, T, len(prefix), len(repeat))
+        return out
+
+    def _consensus_partial(self, w, alleles):
+        """consensus(partial=True): the groups have their shape from the alleles asked for, not from a read."""
+        from .consensus import AlleleConsensus
+        b = w.batch
+        group_of, groups, longest = {}, [], {}
+        for g, want in enumerate(alleles):
+            want = sorted(set(int(x) for x in want if int(x) >= 1))
+            for a in want:
+                group_of[(g, a)] = len(groups)
+                groups.append((g, a))
+            if want:
+                longest[g] = (want[-1], want[-2] if len(want) > 1 else 0)
+        out = [{} for _ in range(b.n_units)]
+        if not groups:
+            return out
+        ng = len(groups)
+        T_of = [len(b.ladder_keys[g][0]) + len(b.ladder_keys[g][1]) * a + len(b.ladder_keys[g][2]) for g, a in groups]
+        stride = max(T_of) + 1
+        n_full, n_part, n_amb, n_beyond = (np.zeros(ng, np.int64) for _ in range(4))
+        counts = np.zeros((ng, stride, _lib.PILEUP_CHANNELS), np.int32)
+        m_all = len(w.items)
+        gid, anchor = np.full(m_all, -1, np.int32), np.zeros(m_all, np.int32)
+        for j in range(m_all):
+            g, h, t = int(w.unit_of[j]), int(w.h[j]), int(w.tag[j])
+            if t == _lib.TAG_FULL:
+                k = group_of.get((g, h), -1)
+                if k >= 0:
+                    gid[j] = k
+                    n_full[k] += 1
+            elif t in (_lib.TAG_PREF, _lib.TAG_POST) and g in longest:
+                a_k, a_prev = longest[g]
+                k = group_of[(g, a_k)]
+                if h > a_k:
+                    n_beyond[k] += 1
+                elif h <= a_prev:
+                    n_amb[k] += 1
+                else:
+                    gid[j], anchor[j] = k, _lib.PILEUP_ANCHOR_BEGIN if t == _lib.TAG_PREF else _lib.PILEUP_ANCHOR_END
+                    n_part[k] += 1
+        sel = np.nonzero(gid >= 0)[0]
+        m = len(sel)
+        if m:
+            packed, woff, rlen = _gather_reads(w.packed, w.read_off, w.read_len, sel)
+            status = np.zeros(m, np.int32)
+            arr = lambda x, dt: np.ascontiguousarray(x[sel], dt)
+            reg = self._register(b.ladder_keys)
+            self.ctx.pileup_anchored(packed, woff, rlen, m, arr(w.item_ladder, np.int32), arr(w.win, np.int32),
+                                     arr(w.fields, np.int16), arr(w.ops, np.uint32), w.cap, arr(w.n_ops, np.int32),
+                                     arr(gid, np.int32), arr(anchor, np.int32), ng,
+                                     np.ascontiguousarray([reg[g] for g, _ in groups], np.int32),
+                                     np.ascontiguousarray([a for _, a in groups], np.int32), stride, counts, status,
+                                     ladders=self._ladders)
+            if (status != _lib.PILEUP_OK).any():
+                k = int(np.nonzero(status != _lib.PILEUP_OK)[0][0])
+                j = int(sel[k])
+                raise _lib.TredGpuError("pileup_anchored: status {} for read {} of unit {}".format(
+                    int(status[k]), int(w.items[j] - b.unit_read_off[w.unit_of[j]]), int(w.unit_of[j])))
+        for k, (g, a) in enumerate(groups):
+            prefix, repeat, suffix, _ = b.ladder_keys[g]
+            out[g][a] = AlleleConsensus(a, n_full[k], counts[k, :T_of[k] + 1], prefix + repeat * a + suffix, len(prefix),
+                                        len(repeat), partial=n_part[k], ambiguous=n_amb[k], beyond=n_beyond[k])
         return out
 
     # ---- the whole path ------------------------------------------------------------------------------

@@ -69,6 +69,13 @@ class _Parser(argparse.ArgumentParser):
         sys.exit(1)
 
 
+class _AlsoConsensus(argparse.Action):
+    """--consensus-partial: the flag itself, and --consensus with it."""
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, True)
+        namespace.consensus = True
+
+
 def set_argparse():
     names = sorted(TREDsRepo().names)
     p = _Parser(prog="tred.py", description=__doc__.split("\n\n")[0],
@@ -89,6 +96,10 @@ def set_argparse():
     p.add_argument("--consensus", action="store_true",
                    help="also write <samplekey>.consensus.json: per called allele the consensus of the reads that span it, its "
                         "depth, the interruptions of the tract and the insertions")
+    p.add_argument("--consensus-partial", dest="consensus_partial", action=_AlsoConsensus, nargs=0, default=False,
+                   help="--consensus, with the reads that begin in a flank and end inside the tract (PREF / POST) laid on the "
+                        "longest called allele from the side of their flank: an allele longer than the reads is covered too. "
+                        "Adds `partial`, `ambiguous` and `beyond` to every allele of the file")
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     p.add_argument("--toy", action="store_true", help=argparse.SUPPRESS)
     g = p.add_argument_group("Performance options")
@@ -255,7 +266,7 @@ def _genotype(engine, picks, o):
             if o["alignments"]:
                 br.alignments = engine.alignments(batch, winners=winners)
             if o["consensus"]:
-                br.consensus = engine.consensus(batch, _called_alleles(br), winners=winners)
+                br.consensus = engine.consensus(batch, _called_alleles(br), winners=winners, partial=o["consensus_partial"])
         i = 0
         for si, _, ks in sub:
             if ks:
@@ -284,16 +295,17 @@ def _called_alleles(br):
     return [sorted({int(c["h1"]) // int(p), int(c["h2"]) // int(p)}) if int(c["status"]) == 0 else [] for c, p in zip(calls, period)]
 
 
-def consensus_text(scan, calls, res):
+def consensus_text(scan, calls, res, partial=False):
     """--consensus: {locus: {"alleles": [AlleleConsensus.to_dict(), ...]}} for every called locus, one entry per distinct
-    called allele of at least one unit, smaller first; sorted keys.  res: {locus index: UnitResult with .consensus}."""
+    called allele of at least one unit, smaller first; sorted keys.  res: {locus index: UnitResult with .consensus}.
+    partial (--consensus-partial): every allele with its `partial`, `ambiguous` and `beyond` counts."""
     out = {}
     for k, name in enumerate(scan.names):
         r = res.get(k)
         if r is None or name + ".details" not in calls:
             continue
         alleles = sorted(set(int(a) for a in (calls[name + ".1"], calls[name + ".2"]) if int(a) >= 1))
-        out[name] = {"alleles": [r.consensus[a].to_dict() for a in alleles]}
+        out[name] = {"alleles": [r.consensus[a].to_dict(partial=partial) for a in alleles]}
     return json.dumps(out, sort_keys=True, indent=1) + "\n"
 
 
@@ -333,7 +345,7 @@ def genotype_scans(engine, task_args, scans):
         o = _options(arg)
         # (a scan whose reads the device selected and still holds -- feeder._device_scan -- goes to the call that packs them there)
         on_device = getattr(pick[1], "device", None) is not None
-        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", o["alignments"], o["consensus"], on_device)
+        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", o["alignments"], o["consensus"], o["consensus_partial"], on_device)
         groups.setdefault(key, (o, []))[1].append(pick)
     parts = {}
 
@@ -891,7 +903,8 @@ def main(args, quiet=False):
         if args.checkexists and not spawned:
             samples = [s for s in samples if not os.path.exists(s[0] + ".json")]
         tasks = [(key, bam, repo, [only] if only else loci, args.maxinsert, args.fullsearch, args.useclippedreads,
-                  not args.noalts, not args.norepeatpairs, args.log) + ((args.alignments, args.consensus) if args.alignments or args.consensus else ())
+                  not args.noalts, not args.norepeatpairs, args.log) + ((args.alignments, args.consensus) if args.alignments or args.consensus else ()) +
+                 ((args.consensus_partial,) if args.consensus_partial else ())
                  for key, bam, only in samples]
         if not tasks:
             return
