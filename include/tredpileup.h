@@ -104,7 +104,44 @@ int tredpileup_pileup_anchored(tredgpu_ctx* ctx, int32_t n_ladders, const char* 
                                const int32_t* n_ops, const int32_t* item_group, const int32_t* item_anchor, int32_t n_groups,
                                const int32_t* group_ladder, const int32_t* group_units, int32_t stride, int32_t* out_counts,
                                int32_t* out_status);
-/* calls of tredpileup_pileup and tredpileup_pileup_anchored on this context since tredpileup_reset_timing and the summed device time of their kernels
+/*
+ * The repeat-unit spectrum of the same items: per group which repeat-unit words (CAG, CAA, CCG, ...) its items show and how
+ * often, per item how many of its units are not the motif.  Position-free, so it takes every tagged read, the in-repeat
+ * ones included, which no pileup can place.  The items as tredpileup_pileup takes them, and
+ *   group_ladder[n_groups]   the group's ladder: the shape of a group is given, so every refusal is the item's own
+ * Counting.  With P, p, S the lengths of prefix, repeat and suffix, an item of template index tpl has h = tpl / 2 + 1
+ * units, strand tpl & 1 and T_h = P + p * h + S columns.  Its own column c is forward column c on strand 0 and T_h - 1 - c
+ * on strand 1, and a read letter counts as itself on strand 0 and complemented on strand 1 (N stays N), as in
+ * tredpileup_pileup.  Tract unit k (0 <= k < h) is the forward columns [P + p * k, P + p * (k + 1)).  A unit is CLEAN for
+ * an item iff all its p forward columns lie inside ONE M operation of the item: a unit cut by an I, a D, a soft clip or the
+ * end of the alignment is not clean; an I exactly on a unit boundary leaves both neighbours clean.  The unit's WORD is the p
+ * read letters on those columns in forward order (on strand 1 the read is walked backwards and complemented).  A word with
+ * an N adds 1 to with_n; any other adds 1 to bin code = sum letter_i * 4^(p - 1 - i), A 0 C 1 G 2 T 3.  A unit is TOUCHED
+ * if at least one of its columns lies in the item's forward span ref_begin .. ref_end, D columns included.
+ *   out_spectrum       int32 [n_groups][TREDGPU_SPECTRUM_STRIDE], written whole: bins 0 .. 4^p - 1 (zero above), then at
+ *                      TREDGPU_SPECTRUM_BINS + 0 the clean units (N-free words plus with_n), + 1 with_n, + 2 the touched
+ *                      units, + 3 the accepted items
+ *   out_item           int32 [n_items][3]: the item's N-free clean units, how many of them equal the ladder's repeat, and
+ *                      its touched units; zeros for a refused item
+ *   out_status[n_items]
+ * Refused per item: everything tredpileup_pileup refuses on an item of its own (TOO_LONG, then BAD_ITEM); BAD_ITEM for
+ * item_ladder other than group_ladder[group] and for a ladder without a tract (max_units <= 0); TREDGPU_PILEUP_PERIOD for a
+ * period above TREDGPU_SPECTRUM_MAX_PERIOD (the table has 4^p bins).
+ * Every row is owned by one workgroup, which adds in LDS and stores once: exact, and independent of the order of the items.
+ * Returns as tredpileup_pileup; -2 (nothing written) also for a NULL array, a group_ladder out of range and n_groups < 0.
+ * Host memory only; the same state, stream and staging, and tredpileup_get_timing counts its calls too.
+ */
+#define TREDGPU_PILEUP_PERIOD 6         /* out_status of tredpileup_unit_spectrum: the ladder's period has no table */
+#define TREDGPU_SPECTRUM_MAX_PERIOD 6
+#define TREDGPU_SPECTRUM_BINS 4096      /* 4^TREDGPU_SPECTRUM_MAX_PERIOD */
+#define TREDGPU_SPECTRUM_STRIDE 4100    /* the bins, then clean, with_n, touched, accepted items */
+int tredpileup_unit_spectrum(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat,
+                             const char* const* suffix, const int32_t* max_units, const uint32_t* packed,
+                             const int64_t* read_off, const int32_t* read_len, int64_t n_items, const int32_t* item_ladder,
+                             const int32_t* item_template, const int16_t* fields, const uint32_t* ops, int32_t cap,
+                             const int32_t* n_ops, const int32_t* item_group, int32_t n_groups, const int32_t* group_ladder,
+                             int32_t* out_spectrum, int32_t* out_item, int32_t* out_status);
+/* calls of the three entries above on this context since tredpileup_reset_timing and the summed device time of their kernels
    (HIP events, one pair around the launches of a call) */
 int tredpileup_get_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms);
 int tredpileup_reset_timing(tredgpu_ctx* ctx);

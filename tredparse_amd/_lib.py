@@ -69,11 +69,15 @@ SECOND_EXPORTS = ("tredsecond_sw_second", "tredsecond_get_timing", "tredsecond_r
 SECOND_OK, SECOND_TOO_LONG, SECOND_BAD_ITEM = 0, 4, 5
 
 # the pileup's symbols (include/tredpileup.h)
-PILEUP_EXPORTS = ("tredpileup_pileup", "tredpileup_pileup_anchored", "tredpileup_get_timing", "tredpileup_reset_timing",
-                  "tredpileup_release", "tredpileup_last_error")
+PILEUP_EXPORTS = ("tredpileup_pileup", "tredpileup_pileup_anchored", "tredpileup_unit_spectrum", "tredpileup_get_timing",
+                  "tredpileup_reset_timing", "tredpileup_release", "tredpileup_last_error")
 PILEUP_OK, PILEUP_TOO_LONG, PILEUP_BAD_ITEM = 0, 4, 5
 PILEUP_ANCHOR_WHOLE, PILEUP_ANCHOR_BEGIN, PILEUP_ANCHOR_END = 0, 1, 2   # item_anchor of pileup_anchored: FULL, PREF, POST
 PILEUP_CHANNELS = 8             # A C G T N, deleted, insertions before the column, their summed length
+PILEUP_PERIOD = 6               # out_status of unit_spectrum: a period above SPECTRUM_MAX_PERIOD has no table
+SPECTRUM_MAX_PERIOD = 6
+SPECTRUM_BINS = 4096            # 4^6 words, code = sum letter_i * 4^(p - 1 - i), A 0 C 1 G 2 T 3
+SPECTRUM_STRIDE = 4100          # the bins, then clean units, with_n, touched units, accepted items
 
 # every symbol include/tredgpu.h declares (tests check the .so exports them all)
 EXPORTS = ("tredgpu_create", "tredgpu_destroy", "tredgpu_last_error", "tredgpu_sync", "tredgpu_get_stream",
@@ -134,6 +138,8 @@ def load():
                                       vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp]
     lib.tredpileup_pileup_anchored.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                                vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
+    lib.tredpileup_unit_spectrum.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                             vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
     for prefix, get_timing, reset_timing, _, last_error in SIDE_UNITS:
         getattr(lib, get_timing).argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
         getattr(lib, reset_timing).argtypes = [vp]
@@ -654,6 +660,20 @@ class Context:
                                                  _ptr(group_ladder), _ptr(group_units), stride, _ptr(out_counts),
                                                  _ptr(out_status))
         self._chk_side(rc, "tredpileup_pileup_anchored failed ({})".format(rc), self.lib.tredpileup_last_error)
+
+    def unit_spectrum(self, packed, read_off, read_len, n_items, item_ladder, item_template, fields, ops, cap, n_ops,
+                      item_group, n_groups, group_ladder, out_spectrum, out_item, out_status, ladders=None):
+        """tredpileup_unit_spectrum (include/tredpileup.h): the items of pileup, counted per group by the repeat-unit
+        words they show whole inside one M operation.  group_ladder: int32 [n_groups]; out_spectrum: int32
+        [n_groups][SPECTRUM_STRIDE] (bins 0 .. 4^p - 1, then at SPECTRUM_BINS clean units, with_n, touched units, accepted
+        items); out_item: int32 [n][3] (N-free clean units, those equal to the repeat, touched units); out_status: int32
+        [n] (PILEUP_*, PILEUP_PERIOD for a period above SPECTRUM_MAX_PERIOD).  Everything else as pileup takes it."""
+        table = _ladder_args(list(self.ladders if ladders is None else ladders))
+        rc = self.lib.tredpileup_unit_spectrum(self.h, *table, _ptr(packed), _ptr(read_off), _ptr(read_len), n_items,
+                                               _ptr(item_ladder), _ptr(item_template), _ptr(fields), _ptr(ops), cap,
+                                               _ptr(n_ops), _ptr(item_group), n_groups, _ptr(group_ladder),
+                                               _ptr(out_spectrum), _ptr(out_item), _ptr(out_status))
+        self._chk_side(rc, "tredpileup_unit_spectrum failed ({})".format(rc), self.lib.tredpileup_last_error)
 
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")

@@ -25,6 +25,15 @@
 // group, so pileup_anchored_kernel needs no first-item search, and an item of h < a units is counted by the SAME walker
 // (count_item) with a window of its forward columns and slots and a shift -- the flank it is anchored in and the tract
 // next to it land where they lie on the group's template, what it shows of the other flank is cut.
+//
+// tredpileup_unit_spectrum is position-free: per group the words of the repeat units its items show whole, per item how
+// many of them are the motif.  validate_spectrum_kernel adds its refusals (the group's ladder, a tract, a period of at
+// most 6); spectrum_kernel, one workgroup of four wavefronts per GROUP, keeps the 4^p bins and four sums in LDS (16 400 B),
+// its wavefronts take the group's items in turn, and the lanes of one spread over the units that lie whole inside ONE M
+// operation and add their word for themselves (ds_add_u32).  In a real tract nearly every lane adds to the motif's bin;
+// counting that word with a ballot and one add per wave instead was measured and bought nothing -- the walk waits for an
+// item's loads, not for LDS (DESIGN) -- so there is one path.  The row is stored once, whole: no global atomic, exact and
+// order-free.
 #include <climits>
 #include <cstring>
 
@@ -61,8 +70,9 @@ struct PileArgs {
     int32_t* out_counts;       // [n_groups][stride][CH]
     int32_t* out_status;
     const int32_t *item_anchor, *group_ladder, *group_units;     // the anchored entry's; NULL otherwise
-    const uint8_t* letters;    // fill_table's other fields, which no kernel of this unit reads
+    const uint8_t* letters;    // fill_table's other fields: the letters are read by spectrum_kernel alone (the motif)
     int32_t match, mismatch, gap_open, gap_extend;
+    int32_t* out_item;         // [n_items][3], the spectrum entry's; its row of a group is out_counts [n_groups][SROW]
 };
 
 __device__ int validate(const PileArgs& a, int64_t item) {
@@ -121,6 +131,10 @@ __global__ __launch_bounds__(256) void validate_anchored_kernel(PileArgs a) {
     a.out_status[item] = status;
 }
 
+// one operation of an item: M = 0, I = 1, D = 2 and its length
+struct Op { int op, len; };
+__device__ __forceinline__ Op op_of(uint32_t v) { return {(int)(v & 15u), (int)(v >> 4)}; }
+
 // The forward columns [col_lo, col_hi) and slots [slot_lo, slot_hi) of an item's OWN template that count, and what is added
 // to them on the way to the group's table.  whole(T): all of a template of T columns, where it lies.
 struct Window { int col_lo, col_hi, slot_lo, slot_hi, shift; };
@@ -144,7 +158,7 @@ __device__ __forceinline__ void count_item(const PileArgs& a, int64_t item, int 
     const int n = a.n_ops[item];
     int r = ref_begin, q = fl[3];
     for (int j = 0; j < n; ++j) {
-        const int op = (int)(ops[j] & 15u), len = (int)(ops[j] >> 4);
+        const auto [op, len] = op_of(ops[j]);
         if (op == 1) {                                             // an insertion before column r of the item's strand
             const int fwd = strand ? T - r : r, slot = fwd - org;
             if (lane == 0 && fwd >= w.slot_lo && fwd < w.slot_hi && slot >= 0 && slot < TILE) {
@@ -252,15 +266,137 @@ __global__ __launch_bounds__(THREADS) void pileup_anchored_kernel(PileArgs a) {
     }
 }
 
+// ---- the repeat-unit spectrum ------------------------------------------------------------------------------------------
+constexpr int BINS = TREDGPU_SPECTRUM_BINS, SROW = TREDGPU_SPECTRUM_STRIDE, MAX_PERIOD = TREDGPU_SPECTRUM_MAX_PERIOD;
+static_assert(BINS == 1 << (2 * MAX_PERIOD) && SROW == BINS + 4, "the row is 4^6 bins and four sums");
+
+// validate, then what the spectrum entry asks of an item against its group: the group's ladder, a ladder with a tract,
+// and a period the table has bins for
+__device__ int validate_spectrum(const PileArgs& a, int64_t item) {
+    const int status = validate(a, item);
+    if (status != TREDGPU_PILEUP_OK) return status;
+    const int g = a.item_group[item], lad = a.item_ladder[item];   // both in range: validate has looked
+    if (lad != a.group_ladder[g] || a.ladders[lad].max_units <= 0) return TREDGPU_PILEUP_BAD_ITEM;
+    if (a.ladders[lad].period > MAX_PERIOD) return TREDGPU_PILEUP_PERIOD;
+    return TREDGPU_PILEUP_OK;
+}
+
+__global__ __launch_bounds__(256) void validate_spectrum_kernel(PileArgs a) {
+    const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= a.n_items) return;
+    const int status = validate_spectrum(a, item);
+    a.pre[item] = status;
+    a.out_status[item] = status;
+    for (int k = 0; k < 3; ++k) a.out_item[item * 3 + k] = 0;      // (an accepted item's triple is spectrum_kernel's)
+}
+
+// what one accepted item adds: units whole inside one M operation (clean), those of them with an N, those equal to the
+// motif, and the units its span touches.  All four are the same in every lane.
+struct Units { int clean, with_n, motif, touched; };
+
+// One accepted item of a ladder (P, p, S: the lengths of prefix, repeat, suffix; motif: the repeat's code, -1 with an N)
+// into the group's bins.  The whole wavefront is here with the same item.
+__device__ __forceinline__ Units spectrum_item(const PileArgs& a, int item, int P, int p, int S, int motif, int* spec) {
+    const int lane = threadIdx.x & 63;
+    const int tpl = a.item_template[item], h = tpl / 2 + 1, strand = tpl & 1, T = P + p * h + S;
+    const int16_t* fl = a.fields + (size_t)item * 5;
+    const int ref_begin = fl[1], ref_end = fl[2];
+    Units u = {0, 0, 0, 0};
+    // the span in forward columns, D columns included, cut to the tract [P, P + p h)
+    const int tlo = max(strand ? T - 1 - ref_end : ref_begin, P), thi = min(strand ? T - 1 - ref_begin : ref_end, P + p * h - 1);
+    if (tlo <= thi) u.touched = (thi - P) / p - (tlo - P) / p + 1;
+    const uint32_t* rec = a.packed + a.read_off[item];
+    const int nb = (a.read_len[item] + 15) >> 4;
+    const uint32_t* ops = a.ops + (size_t)item * a.cap;
+    const int n = a.n_ops[item];
+    int r = ref_begin, q = fl[3];
+    for (int j = 0; j < n; ++j) {
+        const auto [op, len] = op_of(ops[j]);
+        if (op == 0) {
+            // the operation's forward columns [fa, fb) and the units [k_lo, k_hi) that lie whole inside them
+            const int fa = strand ? T - r - len : r, fb = fa + len;
+            const int k_lo = (max(fa, P) - P + p - 1) / p, k_hi = fb > P ? min(h, (fb - P) / p) : 0;
+            for (int k0 = k_lo; k0 < k_hi; k0 += 64) {
+                const int k = k0 + lane;
+                const bool on = k < k_hi;
+                int code = 0;
+                bool has_n = false;
+                if (on)
+                    for (int i = 0; i < p; ++i) {                  // forward order: on strand 1 the read backwards, complemented
+                        const int f = P + p * k + i, c = strand ? T - 1 - f : f;
+                        const int x = read_code(rec, nb, q + (c - r));
+                        has_n |= x > 3;
+                        code = code * 4 + ((strand ? 3 - x : x) & 3);
+                    }
+                const bool word = on && !has_n;
+                if (word) atomicAdd(&spec[code], 1);
+                u.clean += min(64, k_hi - k0);
+                u.with_n += __popcll(__ballot(on && has_n));
+                u.motif += __popcll(__ballot(word && code == motif));
+            }
+        }
+        if (op != 1) r += len;
+        if (op != 2) q += len;
+    }
+    return u;
+}
+
+__global__ __launch_bounds__(THREADS) void spectrum_kernel(PileArgs a) {
+    __shared__ int spec[SROW];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
+        const int64_t lo = a.goff[g], hi = a.goff[g + 1];
+        __syncthreads();                                           // the group before has stored its row
+        for (int k = threadIdx.x; k < SROW; k += THREADS) spec[k] = 0;
+        __syncthreads();
+        const LadderRecord d = a.ladders[a.group_ladder[g]];       // (in range: the host has looked)
+        const int P = d.alen[0], p = d.period, S = d.blen[0];
+        if (d.max_units > 0 && p >= 1 && p <= MAX_PERIOD) {        // (otherwise validate_spectrum has accepted no item)
+            int motif = 0;
+            for (int i = 0; i < p; ++i) {
+                const int c = a.letters[d.trunk_off[0] + P + i];
+                motif = (c > 3 || motif < 0) ? -1 : motif * 4 + c;
+            }
+            Units sum = {0, 0, 0, 0};
+            int accepted = 0;
+            for (int64_t k = lo + wave; k < hi; k += WAVES) {
+                const int item = __builtin_amdgcn_readfirstlane(a.order[k]);
+                if (a.pre[item] != TREDGPU_PILEUP_OK) continue;
+                const Units u = spectrum_item(a, item, P, p, S, motif, spec);
+                if (lane == 0) {
+                    int32_t* out = a.out_item + (size_t)item * 3;
+                    out[0] = u.clean - u.with_n; out[1] = u.motif; out[2] = u.touched;
+                }
+                sum.clean += u.clean; sum.with_n += u.with_n; sum.touched += u.touched;
+                accepted += 1;
+            }
+            if (lane == 0 && accepted) {
+                atomicAdd(&spec[BINS + 0], sum.clean);
+                atomicAdd(&spec[BINS + 1], sum.with_n);
+                atomicAdd(&spec[BINS + 2], sum.touched);
+                atomicAdd(&spec[BINS + 3], accepted);
+            }
+        }
+        __syncthreads();
+        int32_t* out = a.out_counts + (size_t)g * SROW;
+        for (int k = threadIdx.x; k < SROW; k += THREADS) out[k] = spec[k];
+    }
+}
+
 struct State : StateBase {};
 Registry<State> g_states;
 
-// Both entries.  anchor / group_ladder / group_units: the anchored entry's three arrays, all NULL for tredpileup_pileup.
+// The three entries.  anchor / group_ladder / group_units: the anchored entry's three arrays, all NULL for
+// tredpileup_pileup.  The spectrum entry has group_ladder of them, out_item, and its row (SROW int32) where the others have
+// stride columns of CH channels.
+enum Entry { PLAIN, ANCHORED, SPECTRUM };
 int run(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat, const char* const* suffix,
         const int32_t* max_units, const uint32_t* packed, const int64_t* read_off, const int32_t* read_len, int64_t n_items,
         const int32_t* item_ladder, const int32_t* item_template, const int16_t* fields, const uint32_t* ops, int32_t cap,
         const int32_t* n_ops, const int32_t* item_group, int32_t n_groups, int32_t stride, int32_t* out_counts,
-        int32_t* out_status, bool anchored, const int32_t* item_anchor, const int32_t* group_ladder, const int32_t* group_units) {
+        int32_t* out_status, Entry entry, const int32_t* item_anchor, const int32_t* group_ladder, const int32_t* group_units,
+        int32_t* out_item) {
+    const bool anchored = entry == ANCHORED, spectrum = entry == SPECTRUM;
     std::string& err = g_pileup_error;
     err.clear();
     const Table t{n_ladders, prefix, repeat, suffix, max_units};
@@ -271,10 +407,11 @@ int run(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const ch
     if (n_groups < 0 || (n_groups > 0 && !out_counts)) return fail(err, -2, "n_groups must not be negative, nor out_counts NULL");
     if (anchored && ((n_items > 0 && !item_anchor) || (n_groups > 0 && (!group_ladder || !group_units))))
         return fail(err, -2, "NULL array argument");
+    if (spectrum && ((n_items > 0 && !out_item) || (n_groups > 0 && !group_ladder))) return fail(err, -2, "NULL array argument");
     size_t longest = 0;
     for (int i = 0; i < n_ladders; ++i) {
         if (!prefix[i] || !repeat[i] || !suffix[i]) return fail(err, -2, "ladder %d: NULL sequence", i);
-        if (anchored) continue;
+        if (entry != PLAIN) continue;
         const size_t T = max_units[i] > 0 ? strlen(prefix[i]) + strlen(suffix[i]) + strlen(repeat[i]) * (size_t)max_units[i]
                                           : strlen(prefix[i]);
         longest = std::max(longest, std::min<size_t>(T, TREDGPU_MAX_LONG_TEMPLATE_LEN));
@@ -285,12 +422,15 @@ int run(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const ch
         if (group_units[g] < 1) return fail(err, -2, "group %d: units %d must be at least 1", g, group_units[g]);
         longest = std::max(longest, strlen(prefix[lad]) + strlen(suffix[lad]) + strlen(repeat[lad]) * (size_t)group_units[g]);
     }
-    if (stride <= 0 || (size_t)stride < longest + 1 || stride > TREDGPU_PILEUP_MAX_STRIDE)
+    for (int g = 0; spectrum && g < n_groups; ++g)
+        if (group_ladder[g] < 0 || group_ladder[g] >= n_ladders) return fail(err, -2, "group %d: ladder %d out of range", g, group_ladder[g]);
+    if (!spectrum && (stride <= 0 || (size_t)stride < longest + 1 || stride > TREDGPU_PILEUP_MAX_STRIDE))
         return fail(err, -2, "stride %d must be at least the largest template length + 1 = %zu and at most %d", stride,
                     longest + 1, TREDGPU_PILEUP_MAX_STRIDE);
-    const size_t n = (size_t)n_items, cells = (size_t)n_groups * stride * CH;
+    const size_t n = (size_t)n_items, cells = (size_t)n_groups * (spectrum ? (size_t)SROW : (size_t)stride * CH);
     if (n_items == 0 || n_groups == 0) {                           // nothing to launch: the table is written whole all the same
         if (cells) memset(out_counts, 0, cells * 4);
+        if (spectrum && n) memset(out_item, 0, n * 3 * 4);
         for (size_t k = 0; k < n; ++k) out_status[k] = TREDGPU_PILEUP_BAD_ITEM;     // (no group is in range)
         return 0;
     }
@@ -318,12 +458,19 @@ int run(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const ch
         arrays.push_back(arr_in(a.group_ladder, group_ladder, (size_t)n_groups));
         arrays.push_back(arr_in(a.group_units, group_units, (size_t)n_groups));
     }
+    if (spectrum) {
+        arrays.push_back(arr_in(a.group_ladder, group_ladder, (size_t)n_groups));
+        arrays.push_back(arr_out(a.out_item, out_item, n * 3));
+    }
     if ((rc = stage(err, s, st, arrays))) return rc;
     a.n_items = n_items; a.cap = cap; a.n_groups = n_groups; a.stride = stride; a.ntile = (stride + TILE - 1) / TILE;
 
     if ((rc = timed_begin(err, s, st))) return rc;
     const dim3 per_item((unsigned)((n + 255) / 256)), per_tile((unsigned)std::min<int64_t>((int64_t)n_groups * a.ntile, MAX_BLOCKS));
-    if (anchored) {
+    if (spectrum) {
+        hipLaunchKernelGGL(validate_spectrum_kernel, per_item, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(spectrum_kernel, dim3((unsigned)std::min(n_groups, MAX_BLOCKS)), dim3(THREADS), 0, st, a);
+    } else if (anchored) {
         hipLaunchKernelGGL(validate_anchored_kernel, per_item, dim3(256), 0, st, a);
         hipLaunchKernelGGL(pileup_anchored_kernel, per_tile, dim3(THREADS), 0, st, a);
     } else {
@@ -344,7 +491,7 @@ int tredpileup_pileup(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* pr
                       const int16_t* fields, const uint32_t* ops, int32_t cap, const int32_t* n_ops, const int32_t* item_group,
                       int32_t n_groups, int32_t stride, int32_t* out_counts, int32_t* out_status) {
     return run(ctx, n_ladders, prefix, repeat, suffix, max_units, packed, read_off, read_len, n_items, item_ladder, item_template,
-               fields, ops, cap, n_ops, item_group, n_groups, stride, out_counts, out_status, false, nullptr, nullptr, nullptr);
+               fields, ops, cap, n_ops, item_group, n_groups, stride, out_counts, out_status, PLAIN, nullptr, nullptr, nullptr, nullptr);
 }
 
 int tredpileup_pileup_anchored(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat,
@@ -355,8 +502,19 @@ int tredpileup_pileup_anchored(tredgpu_ctx* ctx, int32_t n_ladders, const char* 
                                const int32_t* group_ladder, const int32_t* group_units, int32_t stride, int32_t* out_counts,
                                int32_t* out_status) {
     return run(ctx, n_ladders, prefix, repeat, suffix, max_units, packed, read_off, read_len, n_items, item_ladder, item_template,
-               fields, ops, cap, n_ops, item_group, n_groups, stride, out_counts, out_status, true, item_anchor, group_ladder,
-               group_units);
+               fields, ops, cap, n_ops, item_group, n_groups, stride, out_counts, out_status, ANCHORED, item_anchor, group_ladder,
+               group_units, nullptr);
+}
+
+int tredpileup_unit_spectrum(tredgpu_ctx* ctx, int32_t n_ladders, const char* const* prefix, const char* const* repeat,
+                             const char* const* suffix, const int32_t* max_units, const uint32_t* packed,
+                             const int64_t* read_off, const int32_t* read_len, int64_t n_items, const int32_t* item_ladder,
+                             const int32_t* item_template, const int16_t* fields, const uint32_t* ops, int32_t cap,
+                             const int32_t* n_ops, const int32_t* item_group, int32_t n_groups, const int32_t* group_ladder,
+                             int32_t* out_spectrum, int32_t* out_item, int32_t* out_status) {
+    return run(ctx, n_ladders, prefix, repeat, suffix, max_units, packed, read_off, read_len, n_items, item_ladder, item_template,
+               fields, ops, cap, n_ops, item_group, n_groups, SROW, out_spectrum, out_status, SPECTRUM, nullptr, group_ladder,
+               nullptr, out_item);
 }
 
 int tredpileup_get_timing(tredgpu_ctx* ctx, int64_t* launches, double* total_ms) { return timing(g_pileup_error, g_states, ctx, launches, total_ms, false); }

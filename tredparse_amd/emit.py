@@ -20,7 +20,7 @@ class Emitter(object):
     natively (libtredbam.so tredbam_emit_sample_files, include/tredbam.h) on `workers` threads that run WITHOUT the
     interpreter lock -- instead of building every sample's tredCalls dict (format_scans) and printing it (to_json,
     to_vcf) in Python, which was what bounded a driver process.  The text is byte for byte the Python path's
-    (tests/test_emit_native.py).  A sample the native printers do not cover -- --log DEBUG, --alignments, --consensus, a BAM that did not open, a
+    (tests/test_emit_native.py).  A sample the native printers do not cover -- --log DEBUG, --alignments, --consensus, --spectrum, a BAM that did not open, a
     batch the retries cut into single units, names outside ASCII -- goes through the Python path on the same thread.
       echo      print each JSON on stdout as to_json does (one worker then: the order of the samples is kept)
       on_sample called with {'samplekey', 'names', 'printed' (bool per locus), 'first_allele' (units, per locus)} after a
@@ -85,6 +85,10 @@ class Emitter(object):
                 from .tred import consensus_text
                 with open(result["samplekey"] + ".consensus.json", "w") as fp:
                     fp.write(consensus_text(scan, result["tredCalls"], {k: r for (_, k), r in res.items()}, partial=o["consensus_partial"]))
+            if o["spectrum"]:
+                from .tred import spectrum_text
+                with open(result["samplekey"] + ".spectrum.json", "w") as fp:
+                    fp.write(spectrum_text(scan, result["tredCalls"], {k: r for (_, k), r in res.items()}))
         if self.on_sample is not None:
             calls = result["tredCalls"]
             self.on_sample({"samplekey": result["samplekey"], "names": scan.names,
@@ -96,7 +100,7 @@ class Emitter(object):
         import numpy as np
         from . import bamio
         o = _options(arg)
-        native = scan.opened and len(pieces) == 1 and o["log"] != "DEBUG" and not o["alignments"] and not o["consensus"] and getattr(pieces[0][0], "joint_units", None) is not None
+        native = scan.opened and len(pieces) == 1 and o["log"] != "DEBUG" and not o["alignments"] and not o["consensus"] and not o["spectrum"] and getattr(pieces[0][0], "joint_units", None) is not None
         table = self._table(scan.names) if native else None
         if table is None or (self.no_output and self.on_sample is None):
             if not (self.no_output and self.on_sample is None and o["log"] != "DEBUG"):

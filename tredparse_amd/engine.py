@@ -275,7 +275,7 @@ class _SelectedBatch(object):
 class BatchResult(object):
     """Arrays of one genotyped PackedUnits batch; unit(i) gives the per-unit view the callers format."""
     __slots__ = ("batch", "tag", "h", "score", "full", "pref", "rept", "calls", "marg", "joint", "grid", "grid_off",
-                 "joint_units", "repeatpairs", "_emit", "alignments", "consensus")
+                 "joint_units", "repeatpairs", "_emit", "alignments", "consensus", "spectrum")
 
     def unit(self, i):
         b = self.batch
@@ -301,6 +301,8 @@ class BatchResult(object):
         r.alignments = al[i] if al is not None else None           # Engine.alignments' entry of the unit (--alignments)
         co = getattr(self, "consensus", None)
         r.consensus = co[i] if co is not None else None            # Engine.consensus' entry of the unit (--consensus)
+        sp = getattr(self, "spectrum", None)
+        r.spectrum = sp[i] if sp is not None else None             # Engine.spectrum's entry of the unit (--spectrum)
         return r
 
 
@@ -308,7 +310,7 @@ class UnitResult(object):
     """grid: the dense dump {h1, h2, ml1..ml4} per pair (only when asked for); joint: (triples {h1, h2, exp(ml - max)}
     of the pairs >= e^-10, total over all distinct pairs) -- what P_h1h2 is printed from."""
     __slots__ = ("tags", "hs", "scores", "full", "pref", "rept_hist", "rept", "call", "grid", "joint", "P_h1", "P_h2",
-                 "joint_units", "alignments", "consensus")
+                 "joint_units", "alignments", "consensus", "spectrum")
 
 
 class _Winners(object):
@@ -712,6 +714,59 @@ class Engine(object):
             out[g][a] = AlleleConsensus(a, n_full[k], counts[k, :T_of[k] + 1], prefix + repeat * a + suffix, len(prefix),
                                         len(repeat), partial=n_part[k], ambiguous=n_amb[k], beyond=n_beyond[k])
         return out
+
+    # ---- which repeat units the reads of a locus show -------------------------------------------------
+    def spectrum(self, units, alleles, winners=None):
+        """Per unit a spectrum.RepeatSpectrum: the repeat-unit words of the unit's tagged reads, cut by the alignments of
+        self.winners (winners: what it returned, when the caller already has it) and counted in ONE unit_spectrum call
+        for all units.  The classes of a unit: `full:a` for every a >= 1 of alleles[unit] (reads tagged FULL with h == a),
+        `partial` (all PREF and POST reads, wherever consensus(partial=True) would lay them) and `rept` (all REPT reads);
+        HANG reads are in none.  A unit whose period has no table (above _lib.SPECTRUM_MAX_PERIOD) comes back
+        `unsupported` and none of its reads are sent."""
+        from .spectrum import RepeatSpectrum
+        w = self.winners(units) if winners is None else winners
+        b = w.batch
+        group_of, groups = {}, []                                  # (unit, class name) -> group
+        for g in range(b.n_units):
+            if len(b.ladder_keys[g][1]) > _lib.SPECTRUM_MAX_PERIOD:
+                continue
+            want = sorted(set(int(x) for x in alleles[g] if int(x) >= 1))
+            for name in ["full:{}".format(a) for a in want] + ["partial", "rept"]:
+                group_of[(g, name)] = len(groups)
+                groups.append((g, name))
+        ng = len(groups)
+        spec = np.zeros((ng, _lib.SPECTRUM_STRIDE), np.int32)
+        triples = [np.zeros((0, 3), np.int32)] * ng
+        m_all = len(w.items)
+        gid = np.full(m_all, -1, np.int32)
+        names = {_lib.TAG_PREF: "partial", _lib.TAG_POST: "partial", _lib.TAG_REPT: "rept"}
+        for j in range(m_all):
+            g, t = int(w.unit_of[j]), int(w.tag[j])
+            name = "full:{}".format(int(w.h[j])) if t == _lib.TAG_FULL else names.get(t)
+            gid[j] = group_of.get((g, name), -1)
+        sel = np.nonzero(gid >= 0)[0]
+        m = len(sel)
+        if m:
+            packed, woff, rlen = _gather_reads(w.packed, w.read_off, w.read_len, sel)
+            per_item, status = np.zeros((m, 3), np.int32), np.zeros(m, np.int32)
+            arr = lambda x, dt: np.ascontiguousarray(x[sel], dt)
+            reg = self._register(b.ladder_keys)
+            self.ctx.unit_spectrum(packed, woff, rlen, m, arr(w.item_ladder, np.int32), arr(w.win, np.int32),
+                                   arr(w.fields, np.int16), arr(w.ops, np.uint32), w.cap, arr(w.n_ops, np.int32),
+                                   arr(gid, np.int32), ng, np.ascontiguousarray([reg[g] for g, _ in groups], np.int32), spec,
+                                   per_item, status, ladders=self._ladders)
+            if (status != _lib.PILEUP_OK).any():
+                k = int(np.nonzero(status != _lib.PILEUP_OK)[0][0])
+                j = int(sel[k])
+                raise _lib.TredGpuError("unit_spectrum: status {} for read {} of unit {}".format(
+                    int(status[k]), int(w.items[j] - b.unit_read_off[w.unit_of[j]]), int(w.unit_of[j])))
+            by_group = np.argsort(gid[sel], kind="stable")
+            cut = np.searchsorted(gid[sel][by_group], np.arange(ng + 1))
+            triples = [per_item[by_group[cut[k]:cut[k + 1]]] for k in range(ng)]
+        tables = [None if len(b.ladder_keys[g][1]) > _lib.SPECTRUM_MAX_PERIOD else {} for g in range(b.n_units)]
+        for k, (g, name) in enumerate(groups):
+            tables[g][name] = (spec[k], triples[k])
+        return [RepeatSpectrum(b.ladder_keys[g][1], tables[g]) for g in range(b.n_units)]
 
     # ---- the whole path ------------------------------------------------------------------------------
     def genotype(self, units, want_grid=True):

@@ -132,12 +132,12 @@ def _select_plan(o, f, loci, sites, regions, readlen, sexed, p):
     tredgpu_select_task per locus (the position range of bam_parser.py:209-213, the locus' alternative regions) and -- when
     a locus is X-linked -- one plain region task per chrY window of the sex inference, whose pile-up sums come back with
     the loci's.  None when this sample must go through the host's scan: options whose outputs need more than the device
-    path returns (--log DEBUG prints every pair of the grid, --alignments and --consensus the reads' alignments, --norepeatpairs needs the reads' name ids before the tally), a
+    path returns (--log DEBUG prints every pair of the grid, --alignments, --consensus and --spectrum the reads' alignments, --norepeatpairs needs the reads' name ids before the tally), a
     locus the file or the kernels cannot serve (its contig is missing, its template ladder or the reads are too long)."""
     import numpy as np
     from ._lib import SELECT_TASK_DTYPE
     from .bam_parser import MAX_READ_LEN, ladder_fits, selection_range, y_regions
-    if o["log"] == "DEBUG" or o["alignments"] or o["consensus"] or not (o["repeatpairs"] or o["clip"]):
+    if o["log"] == "DEBUG" or o["alignments"] or o["consensus"] or o["spectrum"] or not (o["repeatpairs"] or o["clip"]):
         return None
     if len(sites) == 0 or (sites["tid"] < 0).any() or (p.tasks["n_chunks"] < 0).any() or readlen > MAX_READ_LEN:
         return None

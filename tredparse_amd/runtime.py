@@ -47,12 +47,12 @@ def timeline_dump():
 
 def _options(arg):
     """The reference's run() argument tuple, named; an eleventh member, where there is one, is --alignments, a twelfth
-    --consensus, a thirteenth --consensus-partial."""
+    --consensus, a thirteenth --consensus-partial, a fourteenth --spectrum."""
     samplekey, bam, repo, names, maxinsert, fullsearch, clip, alts, repeatpairs, log = arg[:10]
     return dict(samplekey=samplekey, bam=bam, repo=repo, names=list(names), maxinsert=maxinsert,
                 fullsearch=fullsearch, clip=clip, alts=alts, repeatpairs=repeatpairs, log=log,
                 alignments=bool(arg[10]) if len(arg) > 10 else False, consensus=bool(arg[11]) if len(arg) > 11 else False,
-                consensus_partial=bool(arg[12]) if len(arg) > 12 else False)
+                consensus_partial=bool(arg[12]) if len(arg) > 12 else False, spectrum=bool(arg[13]) if len(arg) > 13 else False)
 
 
 def collect_sample(arg, long_reads=False):

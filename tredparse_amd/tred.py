@@ -100,6 +100,10 @@ def set_argparse():
                    help="--consensus, with the reads that begin in a flank and end inside the tract (PREF / POST) laid on the "
                         "longest called allele from the side of their flank: an allele longer than the reads is covered too. "
                         "Adds `partial`, `ambiguous` and `beyond` to every allele of the file")
+    p.add_argument("--spectrum", action="store_true",
+                   help="also write <samplekey>.spectrum.json: per called locus which repeat-unit words (CAG, CAA, CCG, ...) its "
+                        "reads show and how often -- the spanning, the partial and the in-repeat reads apart -- and how pure "
+                        "the tract is")
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     p.add_argument("--toy", action="store_true", help=argparse.SUPPRESS)
     g = p.add_argument_group("Performance options")
@@ -261,12 +265,14 @@ def _genotype(engine, picks, o):
             return
         br = engine.genotype_packed(batch, dense=True) if o["log"] == "DEBUG" else engine.genotype_packed(batch)
         br.repeatpairs = kw["repeatpairs"]
-        if o["alignments"] or o["consensus"]:
-            winners = engine.winners(batch)                       # classify with the dump and the CIGAR call: once for both
+        if o["alignments"] or o["consensus"] or o["spectrum"]:
+            winners = engine.winners(batch)                       # classify with the dump and the CIGAR call: once for all three
             if o["alignments"]:
                 br.alignments = engine.alignments(batch, winners=winners)
             if o["consensus"]:
                 br.consensus = engine.consensus(batch, _called_alleles(br), winners=winners, partial=o["consensus_partial"])
+            if o["spectrum"]:
+                br.spectrum = engine.spectrum(batch, _called_alleles(br), winners=winners)
         i = 0
         for si, _, ks in sub:
             if ks:
@@ -309,6 +315,18 @@ def consensus_text(scan, calls, res, partial=False):
     return json.dumps(out, sort_keys=True, indent=1) + "\n"
 
 
+def spectrum_text(scan, calls, res):
+    """--spectrum: {locus: RepeatSpectrum.to_dict()} for every called locus; sorted keys.  res: {locus index: UnitResult
+    with .spectrum}."""
+    out = {}
+    for k, name in enumerate(scan.names):
+        r = res.get(k)
+        if r is None or name + ".details" not in calls:
+            continue
+        out[name] = r.spectrum.to_dict()
+    return json.dumps(out, sort_keys=True, indent=1) + "\n"
+
+
 def alignments_text(scan, calls, res, repeatpairs):
     """--alignments: for every `details` entry of every called locus, in `details` order, a header line
     `>{locus} {tag} h={h} {+|-} {read id}` (- : the template's reverse complement), the reference's verbose block for the
@@ -345,7 +363,7 @@ def genotype_scans(engine, task_args, scans):
         o = _options(arg)
         # (a scan whose reads the device selected and still holds -- feeder._device_scan -- goes to the call that packs them there)
         on_device = getattr(pick[1], "device", None) is not None
-        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", o["alignments"], o["consensus"], o["consensus_partial"], on_device)
+        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", o["alignments"], o["consensus"], o["consensus_partial"], o["spectrum"], on_device)
         groups.setdefault(key, (o, []))[1].append(pick)
     parts = {}
 
@@ -904,7 +922,8 @@ def main(args, quiet=False):
             samples = [s for s in samples if not os.path.exists(s[0] + ".json")]
         tasks = [(key, bam, repo, [only] if only else loci, args.maxinsert, args.fullsearch, args.useclippedreads,
                   not args.noalts, not args.norepeatpairs, args.log) + ((args.alignments, args.consensus) if args.alignments or args.consensus else ()) +
-                 ((args.consensus_partial,) if args.consensus_partial else ())
+                 ((args.consensus_partial,) if args.consensus_partial else ()) +
+                 ((False,) * (0 if args.consensus_partial else 1 if args.alignments or args.consensus else 3) + (True,) if args.spectrum else ())
                  for key, bam, only in samples]
         if not tasks:
             return
