@@ -567,13 +567,21 @@ class Context:
     def _cigar_call(self, long_call, mem, ladders, packed, read_off, read_len, n_items, item_ladder, item_template, fields,
                     params, cap, out_ops, out_n_ops, out_status):
         """One call of tredlong_sw_cigar (long_call; host memory only, so it has no mem argument) or tredcigar_sw_cigar."""
-        name = "tredlong_sw_cigar" if long_call else "tredcigar_sw_cigar"
-        table = _ladder_args(ladders)
-        rc = getattr(self.lib, name)(self.h, *(() if long_call else (mem,)), *table, _ptr(packed), _ptr(read_off),
-                                     _ptr(read_len), n_items, _ptr(item_ladder), _ptr(item_template), _ptr(fields),
-                                     C.byref(params), cap, _ptr(out_ops), _ptr(out_n_ops), _ptr(out_status))
-        self._chk_side(rc, "{} failed ({})".format(name, rc),
-                       self.lib.tredlong_last_error if long_call else self.lib.tredcigar_last_error)
+        unit = "tredlong" if long_call else "tredcigar"
+        self._items_call(unit + "_sw_cigar", unit + "_last_error", ladders, packed, read_off, read_len, n_items, item_ladder,
+                         item_template, _ptr(fields), C.byref(params), cap, _ptr(out_ops), _ptr(out_n_ops), _ptr(out_status),
+                         mem=None if long_call else mem)
+
+    def _items_call(self, entry, last_error, ladders, packed, read_off, read_len, n_items, item_ladder, item_template, *tail,
+                    mem=None):
+        """One call of a side unit's item-list entry (include/tredcigar.h, tredlong.h, tredsecond.h, tredpileup.h): the
+        context, mem where the entry takes one (tredcigar_sw_cigar), the ladder table (ladders; None: the one registered
+        with set_ladders), the items -- packed, read_off, read_len, n_items, item_ladder, item_template --, then tail, the
+        entry's own arguments as the library takes them.  A refusal raises with the unit's own last_error."""
+        table = _ladder_args(list(self.ladders if ladders is None else ladders))
+        rc = getattr(self.lib, entry)(self.h, *(() if mem is None else (mem,)), *table, _ptr(packed), _ptr(read_off),
+                                      _ptr(read_len), n_items, _ptr(item_ladder), _ptr(item_template), *tail)
+        self._chk_side(rc, "{} failed ({})".format(entry, rc), getattr(self.lib, last_error))
 
     @staticmethod
     def _chk_side(rc, what, last_error):
@@ -624,11 +632,8 @@ class Context:
         template item_template[k] (db order) of ladder item_ladder[k] with maskLen mask_len[k] (int32 [n]).  out: int32
         [n][4], out_status: int32 [n] (SECOND_*).  ladders: the table the indices refer to (default: the one registered
         with set_ladders).  One unit takes short and long items alike, whether or not the long-read path is on."""
-        table = _ladder_args(list(self.ladders if ladders is None else ladders))
-        rc = self.lib.tredsecond_sw_second(self.h, *table, _ptr(packed), _ptr(read_off), _ptr(read_len), n_items,
-                                           _ptr(item_ladder), _ptr(item_template), _ptr(mask_len), C.byref(params), _ptr(out),
-                                           _ptr(out_status))
-        self._chk_side(rc, "tredsecond_sw_second failed ({})".format(rc), self.lib.tredsecond_last_error)
+        self._items_call("tredsecond_sw_second", "tredsecond_last_error", ladders, packed, read_off, read_len, n_items,
+                         item_ladder, item_template, _ptr(mask_len), C.byref(params), _ptr(out), _ptr(out_status))
 
     def pileup(self, packed, read_off, read_len, n_items, item_ladder, item_template, fields, ops, cap, n_ops, item_group,
                n_groups, stride, out_counts, out_status, ladders=None):
@@ -639,11 +644,9 @@ class Context:
         and their summed length), stride at least the longest template + 1; out_status: int32 [n] (PILEUP_*).  ladders: the
         table the indices refer to (default: the one registered with set_ladders).  One unit takes short and long items
         alike, whether or not the long-read path is on."""
-        table = _ladder_args(list(self.ladders if ladders is None else ladders))
-        rc = self.lib.tredpileup_pileup(self.h, *table, _ptr(packed), _ptr(read_off), _ptr(read_len), n_items,
-                                        _ptr(item_ladder), _ptr(item_template), _ptr(fields), _ptr(ops), cap, _ptr(n_ops),
-                                        _ptr(item_group), n_groups, stride, _ptr(out_counts), _ptr(out_status))
-        self._chk_side(rc, "tredpileup_pileup failed ({})".format(rc), self.lib.tredpileup_last_error)
+        self._items_call("tredpileup_pileup", "tredpileup_last_error", ladders, packed, read_off, read_len, n_items, item_ladder,
+                         item_template, _ptr(fields), _ptr(ops), cap, _ptr(n_ops), _ptr(item_group), n_groups, stride,
+                         _ptr(out_counts), _ptr(out_status))
 
     def pileup_anchored(self, packed, read_off, read_len, n_items, item_ladder, item_template, fields, ops, cap, n_ops,
                         item_group, item_anchor, n_groups, group_ladder, group_units, stride, out_counts, out_status,
@@ -653,13 +656,10 @@ class Context:
         item (item_anchor int32 [n], PILEUP_ANCHOR_*): an item of h < a units keeps the flank it is anchored in and the
         tract next to it, moved to where they lie on the group's template.  stride: at least the longest GROUP template
         + 1.  Everything else as pileup takes it."""
-        table = _ladder_args(list(self.ladders if ladders is None else ladders))
-        rc = self.lib.tredpileup_pileup_anchored(self.h, *table, _ptr(packed), _ptr(read_off), _ptr(read_len), n_items,
-                                                 _ptr(item_ladder), _ptr(item_template), _ptr(fields), _ptr(ops), cap,
-                                                 _ptr(n_ops), _ptr(item_group), _ptr(item_anchor), n_groups,
-                                                 _ptr(group_ladder), _ptr(group_units), stride, _ptr(out_counts),
-                                                 _ptr(out_status))
-        self._chk_side(rc, "tredpileup_pileup_anchored failed ({})".format(rc), self.lib.tredpileup_last_error)
+        self._items_call("tredpileup_pileup_anchored", "tredpileup_last_error", ladders, packed, read_off, read_len, n_items,
+                         item_ladder, item_template, _ptr(fields), _ptr(ops), cap, _ptr(n_ops), _ptr(item_group),
+                         _ptr(item_anchor), n_groups, _ptr(group_ladder), _ptr(group_units), stride, _ptr(out_counts),
+                         _ptr(out_status))
 
     def unit_spectrum(self, packed, read_off, read_len, n_items, item_ladder, item_template, fields, ops, cap, n_ops,
                       item_group, n_groups, group_ladder, out_spectrum, out_item, out_status, ladders=None):
@@ -668,12 +668,9 @@ class Context:
         [n_groups][SPECTRUM_STRIDE] (bins 0 .. 4^p - 1, then at SPECTRUM_BINS clean units, with_n, touched units, accepted
         items); out_item: int32 [n][3] (N-free clean units, those equal to the repeat, touched units); out_status: int32
         [n] (PILEUP_*, PILEUP_PERIOD for a period above SPECTRUM_MAX_PERIOD).  Everything else as pileup takes it."""
-        table = _ladder_args(list(self.ladders if ladders is None else ladders))
-        rc = self.lib.tredpileup_unit_spectrum(self.h, *table, _ptr(packed), _ptr(read_off), _ptr(read_len), n_items,
-                                               _ptr(item_ladder), _ptr(item_template), _ptr(fields), _ptr(ops), cap,
-                                               _ptr(n_ops), _ptr(item_group), n_groups, _ptr(group_ladder),
-                                               _ptr(out_spectrum), _ptr(out_item), _ptr(out_status))
-        self._chk_side(rc, "tredpileup_unit_spectrum failed ({})".format(rc), self.lib.tredpileup_last_error)
+        self._items_call("tredpileup_unit_spectrum", "tredpileup_last_error", ladders, packed, read_off, read_len, n_items,
+                         item_ladder, item_template, _ptr(fields), _ptr(ops), cap, _ptr(n_ops), _ptr(item_group), n_groups,
+                         _ptr(group_ladder), _ptr(out_spectrum), _ptr(out_item), _ptr(out_status))
 
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")

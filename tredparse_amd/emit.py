@@ -70,25 +70,18 @@ class Emitter(object):
 
     def _python_path(self, arg, scan, pieces):
         """The sample through format_scans and the Python writers (what the native path must equal)."""
-        from .tred import format_scans, unit_results, write_vcf_json
+        from .tred import REPORT_TABLE, format_scans, unit_results, write_vcf_json
         picks = [(0, scan, [k for _, _, ks in pieces for k in ks])]
         res = unit_results({0: pieces})
         result = format_scans([arg], [scan], picks, res, lazy_details=True)[0]
         if not self.no_output:
             write_vcf_json(result, self.ref, self.repo, self.treds, quiet=not self.echo)
             o = _options(arg)
-            if o["alignments"]:
-                from .tred import alignments_text
-                with open(result["samplekey"] + ".alignments.txt", "w") as fp:
-                    fp.write(alignments_text(scan, result["tredCalls"], {k: r for (_, k), r in res.items()}, o["repeatpairs"] or o["clip"]))
-            if o["consensus"]:
-                from .tred import consensus_text
-                with open(result["samplekey"] + ".consensus.json", "w") as fp:
-                    fp.write(consensus_text(scan, result["tredCalls"], {k: r for (_, k), r in res.items()}, partial=o["consensus_partial"]))
-            if o["spectrum"]:
-                from .tred import spectrum_text
-                with open(result["samplekey"] + ".spectrum.json", "w") as fp:
-                    fp.write(spectrum_text(scan, result["tredCalls"], {k: r for (_, k), r in res.items()}))
+            per_locus = {k: r for (_, k), r in res.items()}
+            for name in o["reports"]:
+                suffix, _, text = REPORT_TABLE[name]
+                with open(result["samplekey"] + suffix, "w") as fp:
+                    fp.write(text(scan, result["tredCalls"], per_locus, o))
         if self.on_sample is not None:
             calls = result["tredCalls"]
             self.on_sample({"samplekey": result["samplekey"], "names": scan.names,
@@ -100,7 +93,7 @@ class Emitter(object):
         import numpy as np
         from . import bamio
         o = _options(arg)
-        native = scan.opened and len(pieces) == 1 and o["log"] != "DEBUG" and not o["alignments"] and not o["consensus"] and not o["spectrum"] and getattr(pieces[0][0], "joint_units", None) is not None
+        native = scan.opened and len(pieces) == 1 and o["log"] != "DEBUG" and not o["reports"] and pieces[0][0].joint_units is not None
         table = self._table(scan.names) if native else None
         if table is None or (self.no_output and self.on_sample is None):
             if not (self.no_output and self.on_sample is None and o["log"] != "DEBUG"):
@@ -114,7 +107,7 @@ class Emitter(object):
                                      STATUS_ERRORS.get(int(st[j]), "status {}".format(int(st[j]))))
             return
         br, i0, ks = pieces[0]
-        eb = getattr(br, "_emit", None)
+        eb = br._emit
         if eb is None:                       # the batch's arrays, once per batch (whichever sample's thread gets there first)
             a, b, v, lo, n = br.joint_units
             keep = [np.ascontiguousarray(x) for x in (br.tag, br.h, br.batch.unit_read_off, br.calls, br.marg, a, b, v, lo, n)]

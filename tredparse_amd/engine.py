@@ -12,6 +12,7 @@ import os
 import numpy as np
 
 from . import _lib
+from .runtime import REPORTS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SMALL_VALUE = float(np.exp(-10))  # models.py:34
@@ -275,7 +276,11 @@ class _SelectedBatch(object):
 class BatchResult(object):
     """Arrays of one genotyped PackedUnits batch; unit(i) gives the per-unit view the callers format."""
     __slots__ = ("batch", "tag", "h", "score", "full", "pref", "rept", "calls", "marg", "joint", "grid", "grid_off",
-                 "joint_units", "repeatpairs", "_emit", "alignments", "consensus", "spectrum")
+                 "joint_units", "repeatpairs", "_emit") + REPORTS
+
+    def __init__(self):
+        for name in self.__slots__:           # what a producer does not fill is None (the histograms of the fused calls, the
+            setattr(self, name, None)         # dense dump, the reports nobody asked for)
 
     def unit(self, i):
         b = self.batch
@@ -283,26 +288,21 @@ class BatchResult(object):
         r = UnitResult()
         r.tags, r.hs, r.scores = self.tag[a:e], self.h[a:e], self.score[a:e]
         r.full = r.pref = r.rept_hist = None      # the histograms {units: count}: only where the batch has them (not the fused calls)
-        if getattr(self, "full", None) is not None:
+        if self.full is not None:
             r.full, r.pref, r.rept_hist = ({int(k): int(v) for k, v in enumerate(x[i]) if v} for x in (self.full, self.pref, self.rept))
         r.rept = int(self.rept[i].sum())
         r.call = self.calls[i]
-        r.grid = None
-        if getattr(self, "grid", None) is not None and self.calls[i]["status"] == 0:
-            r.grid = self.grid[self.grid_off[i]:self.grid_off[i] + self.calls[i]["n_pairs"]]
-        r.joint = self.joint[i] if self.calls[i]["status"] == 0 and self.joint is not None else None
-        ju = getattr(self, "joint_units", None)
+        called = self.calls[i]["status"] == 0
+        r.grid = self.grid[self.grid_off[i]:self.grid_off[i] + self.calls[i]["n_pairs"]] if called and self.grid is not None else None
+        r.joint = self.joint[i] if called and self.joint is not None else None
         r.joint_units = None
-        if ju is not None and self.calls[i]["status"] == 0:
-            a, b, v, lo, n = ju
+        if called and self.joint_units is not None:
+            a, b, v, lo, n = self.joint_units
             r.joint_units = (a[lo[i]:lo[i] + n[i]], b[lo[i]:lo[i] + n[i]], v[lo[i]:lo[i] + n[i]])
         r.P_h1, r.P_h2 = self.marg[i, 0], self.marg[i, 1]
-        al = getattr(self, "alignments", None)
-        r.alignments = al[i] if al is not None else None           # Engine.alignments' entry of the unit (--alignments)
-        co = getattr(self, "consensus", None)
-        r.consensus = co[i] if co is not None else None            # Engine.consensus' entry of the unit (--consensus)
-        sp = getattr(self, "spectrum", None)
-        r.spectrum = sp[i] if sp is not None else None             # Engine.spectrum's entry of the unit (--spectrum)
+        for name in REPORTS:                      # Engine.alignments' / .consensus' / .spectrum's entry of the unit
+            x = getattr(self, name)
+            setattr(r, name, x[i] if x is not None else None)
         return r
 
 
@@ -310,16 +310,78 @@ class UnitResult(object):
     """grid: the dense dump {h1, h2, ml1..ml4} per pair (only when asked for); joint: (triples {h1, h2, exp(ml - max)}
     of the pairs >= e^-10, total over all distinct pairs) -- what P_h1h2 is printed from."""
     __slots__ = ("tags", "hs", "scores", "full", "pref", "rept_hist", "rept", "call", "grid", "joint", "P_h1", "P_h2",
-                 "joint_units", "alignments", "consensus", "spectrum")
+                 "joint_units") + REPORTS
 
 
 class _Winners(object):
     """Engine.winners' result: the batch, and per tagged read of its units (m of them, in batch order) tag, h, the read's
     index in the batch (items), the winning template (win, db order) and its dump row (best), the unit (unit_of); and the
     arguments and outputs of the sw_cigar call over them (packed / read_off / read_len: the tagged reads gathered from the
-    batch, item_ladder, fields, ops, n_ops, cap).  Without a tagged read only batch and items (empty) are set."""
+    batch, item_ladder, fields, ops, n_ops, cap).  Without a tagged read only batch, items, tag, h and unit_of (all empty)
+    are set."""
     __slots__ = ("batch", "tag", "h", "items", "win", "best", "unit_of", "packed", "read_off", "read_len", "item_ladder",
                  "fields", "ops", "n_ops", "cap")
+
+    def take(self, sel):
+        """The winners `sel` (indices into them, any order, repeats allowed) as an item list of their own, every array
+        C-contiguous: packed u32, read_off i64 [n + 1], read_len i32 (the reads' words gathered), item_ladder i32, win i32,
+        fields i16 [n][5], ops u32 [n][cap], n_ops i32 -- the order every item-list entry of the context takes them in."""
+        sel = np.asarray(sel, np.int64)
+        own = lambda x, dt: np.ascontiguousarray(x[sel], dt)
+        return _gather_reads(self.packed, self.read_off, self.read_len, sel) + (
+            own(self.item_ladder, np.int32), own(self.win, np.int32), own(self.fields, np.int16), own(self.ops, np.uint32),
+            own(self.n_ops, np.int32))
+
+
+# ---- which group of a report a tagged read is counted in: plain arithmetic on (tag, h, unit), no GPU -----------------------
+def _wanted(want):
+    """The alleles asked for of one unit as every report takes them: whole repeat units >= 1, each once, ascending."""
+    return sorted(set(int(x) for x in want if int(x) >= 1))
+
+
+def _group_ids(groups, keys):
+    """int32 per key: its index in groups, -1 for a key that is no group."""
+    group_of = {k: i for i, k in enumerate(groups)}
+    return np.array([group_of.get(k, -1) for k in keys], np.int32)
+
+
+def place_consensus(tag, h, unit_of, alleles, partial=False):
+    """Engine.consensus' rule over the winners' tag, h and unit_of: (groups, gid, anchor, n).  groups: [(unit, a)] for every
+    allele asked for, units then alleles ascending; gid: int32 per winner, its group or -1; anchor: int32 per winner
+    (PILEUP_ANCHOR_*); n: the counters per group, int64 -- "full", "partial", "ambiguous", "beyond".
+    A FULL read goes to (unit, h) when that was asked for.  partial: of a unit whose longest allele asked for is a_k and
+    next longest a_prev (0 when there is none), a PREF / POST read with a_prev < h <= a_k goes to a_k, anchored in its
+    flank; one with h <= a_prev is counted `ambiguous` and one with h > a_k `beyond`, both on a_k and laid nowhere.
+    Every other read has no group."""
+    groups = [(g, a) for g, want in enumerate(alleles) for a in _wanted(want)]
+    gid = _group_ids(groups, [(g, a) if t == _lib.TAG_FULL else None for g, a, t in zip(unit_of.tolist(), h.tolist(), tag.tolist())])
+    anchor = np.zeros(len(gid), np.int32)
+    n = {kind: np.zeros(len(groups), np.int64) for kind in ("partial", "ambiguous", "beyond")}
+    n["full"] = np.bincount(gid[gid >= 0], minlength=len(groups)).astype(np.int64)
+    if partial:
+        longest = {g: k for k, (g, _) in enumerate(groups)}        # (a unit's alleles ascend: its last group is a_k's)
+        anchor_of = {_lib.TAG_PREF: _lib.PILEUP_ANCHOR_BEGIN, _lib.TAG_POST: _lib.PILEUP_ANCHOR_END}
+        for j, (g, x, t) in enumerate(zip(unit_of.tolist(), h.tolist(), tag.tolist())):
+            if t in anchor_of and g in longest:
+                k = longest[g]
+                a_prev = groups[k - 1][1] if k and groups[k - 1][0] == g else 0
+                kind = "beyond" if x > groups[k][1] else "ambiguous" if x <= a_prev else "partial"
+                n[kind][k] += 1
+                if kind == "partial":
+                    gid[j], anchor[j] = k, anchor_of[t]
+    return groups, gid, anchor, n
+
+
+def place_spectrum(tag, h, unit_of, alleles, period):
+    """Engine.spectrum's rule: (groups, gid).  groups: [(unit, class)] -- per unit, ascending, `full:a` for every allele
+    asked for, ascending, then `partial`, then `rept`; a unit whose period (period[unit]) is above
+    _lib.SPECTRUM_MAX_PERIOD has none.  gid: int32 per winner: a FULL read's is (unit, full:h), a PREF or POST read's
+    (unit, partial), a REPT read's (unit, rept) -- -1 where that is no group, and for every other read."""
+    groups = [(g, name) for g, p in enumerate(period) if p <= _lib.SPECTRUM_MAX_PERIOD
+              for name in ["full:{}".format(a) for a in _wanted(alleles[g])] + ["partial", "rept"]]
+    names = {_lib.TAG_PREF: "partial", _lib.TAG_POST: "partial", _lib.TAG_REPT: "rept"}
+    return groups, _group_ids(groups, [(g, "full:{}".format(x) if t == _lib.TAG_FULL else names.get(t))
+                                       for g, x, t in zip(unit_of.tolist(), h.tolist(), tag.tolist())])
 
 
 class ReadAlignment(object):
@@ -463,7 +525,7 @@ class Engine(object):
         batch's ladders registered, call(r, ladder ids, hist_stride, marg_stride, joff, trip, jn, jt) once per attempt of
         the joint read-back, the per-read outputs trimmed to the batch's reads."""
         r = BatchResult()
-        r.batch, r.grid, r.grid_off, r.full, r.pref = b, None, None, None, None
+        r.batch = b
         g, n = b.n_units, b.n_reads
         hs = b.max_units + 2
         ms = _marg_stride(b.params, hs)
@@ -481,7 +543,6 @@ class Engine(object):
         refuse_invalid: raise straight after the SW call when a read came back TAG_INVALID."""
         r = BatchResult()
         r.batch = b
-        r.grid = r.grid_off = None
         r.tag, r.h, r.score = self.classify_packed(b)
         if refuse_invalid:
             _refuse_invalid(r.tag)
@@ -543,7 +604,8 @@ class Engine(object):
         items = np.nonzero(tag != _lib.TAG_NONE)[0]
         m = len(items)
         w = _Winners()
-        w.batch, w.items = b, items
+        unit_of = (np.searchsorted(uro, items, side="right") - 1).astype(np.int64)
+        w.batch, w.items, w.tag, w.h, w.unit_of = b, items, tag[items], h[items], unit_of
         if m == 0:                            # (no tagged read: nothing was asked of sw_cigar)
             return w
         # rows in db order are u=1 fwd, u=1 rc, u=2 fwd, ...: the first row with the highest score has the fewest units
@@ -553,7 +615,6 @@ class Engine(object):
         best = rows[np.arange(m), win]
         assert (best[:, 0] == sc[items]).all() and (best[:, 5] == tag[items]).all() and (win // 2 + 1 == h[items]).all(), \
             "the winning dump row is not the pair the read was tagged for"
-        unit_of = (np.searchsorted(uro, items, side="right") - 1).astype(np.int64)
         w.packed, w.read_off, w.read_len = _gather_reads(b.packed, b.read_off, b.read_len, items)
         fields = np.ascontiguousarray(best[:, :5], np.int16)
         item_ladder = np.ascontiguousarray(self._register(b.ladder_keys)[unit_of])
@@ -565,11 +626,8 @@ class Engine(object):
             if not (status == _lib.CIGAR_OVERFLOW).any():
                 break
             cap = int(n_ops.max())            # (a CIGAR of more than 32 operations: once more with the room it needs)
-        if (status != _lib.CIGAR_OK).any():
-            k = int(np.nonzero(status != _lib.CIGAR_OK)[0][0])
-            raise _lib.TredGpuError("sw_cigar: status {} for read {} of unit {}".format(int(status[k]), int(items[k] - uro[unit_of[k]]),
-                                                                                      int(unit_of[k])))
-        w.tag, w.h, w.win, w.best, w.unit_of = tag[items], h[items], win, best, unit_of
+        _refuse_item("sw_cigar", status, _lib.CIGAR_OK, items, unit_of, uro)
+        w.win, w.best = win, best
         w.item_ladder, w.fields, w.ops, w.n_ops, w.cap = item_ladder, fields, ops, n_ops, cap
         return w
 
@@ -594,6 +652,24 @@ class Engine(object):
         return out
 
     # ---- what is in the tract of an allele --------------------------------------------------------------
+    def _grouped(self, name, w, gid, tail):
+        """ONE call of the context's item-list entry `name` (pileup, pileup_anchored, unit_spectrum) over the winners that
+        have a group (gid >= 0), in their order: the items taken out of w, their groups, tail(sel) -- the entry's arguments
+        between item_group and out_status --, a status per item; an item the entry refuses raises.  No winner with a group:
+        no call.  Returns sel, the winners sent."""
+        sel = np.nonzero(gid >= 0)[0]
+        if len(sel):
+            packed, read_off, read_len, item_ladder, win, fields, ops, n_ops = w.take(sel)
+            status = np.zeros(len(sel), np.int32)
+            getattr(self.ctx, name)(packed, read_off, read_len, len(sel), item_ladder, win, fields, ops, w.cap, n_ops,
+                                    np.ascontiguousarray(gid[sel], np.int32), *tail(sel), status, ladders=self._ladders)
+            _refuse_item(name, status, _lib.PILEUP_OK, w.items[sel], w.unit_of[sel], w.batch.unit_read_off)
+        return sel
+
+    def _group_ladders(self, b, groups):
+        """The registered ladder of every group's unit (int32 [n_groups])."""
+        return np.ascontiguousarray(self._register(b.ladder_keys)[[g for g, _ in groups]], np.int32)
+
     def consensus(self, units, alleles, winners=None, partial=False):
         """Per unit: {a: consensus.AlleleConsensus} for every a >= 1 of alleles[unit] (repeat units): the reads of the
         unit tagged FULL with h == a, laid on prefix + repeat * a + suffix by the alignments of self.winners (winners:
@@ -607,112 +683,30 @@ class Engine(object):
         longest allele asked for is a_k and next longest a_prev (0 when there is none), a partial read with
         a_prev < h <= a_k can only come from a_k and is laid on it from the side of its flank (AlleleConsensus.partial);
         one with h <= a_prev fits any allele asked for and is counted as `ambiguous`, one with h > a_k as `beyond`, both on
-        a_k and laid nowhere.  REPT and HANG reads are never placed."""
+        a_k and laid nowhere.  REPT and HANG reads are never placed.  (The rule: place_consensus.)"""
         from .consensus import AlleleConsensus
         w = self.winners(units) if winners is None else winners
-        if partial:
-            return self._consensus_partial(w, alleles)
         b = w.batch
-        group_of, groups = {}, []
-        for g, want in enumerate(alleles):
-            for a in sorted(set(int(x) for x in want)):
-                if a >= 1:
-                    group_of[(g, a)] = len(groups)
-                    groups.append((g, a))
-        out = [{} for _ in range(b.n_units)]
-        if not groups:
-            return out
-        stride = max(self.ctx._template_len(l) for l in self._ladders) + 1       # (of the table the call is given, not the batch's own)
-        counts, n_reads = None, np.zeros(len(groups), np.int64)
-        if len(w.items):
-            gid = np.array([group_of.get((g, a), -1) if t == _lib.TAG_FULL else -1
-                            for g, a, t in zip(w.unit_of.tolist(), w.h.tolist(), w.tag.tolist())], np.int32)
-            sel = np.nonzero(gid >= 0)[0]
-            m = len(sel)
-            if m:
-                packed, woff, rlen = _gather_reads(w.packed, w.read_off, w.read_len, sel)
-                counts = np.zeros((len(groups), stride, _lib.PILEUP_CHANNELS), np.int32)
-                status = np.zeros(m, np.int32)
-                arr = lambda x, dt: np.ascontiguousarray(x[sel], dt)
-                self.ctx.pileup(packed, woff, rlen, m, arr(w.item_ladder, np.int32), arr(w.win, np.int32), arr(w.fields, np.int16),
-                                arr(w.ops, np.uint32), w.cap, arr(w.n_ops, np.int32), arr(gid, np.int32), len(groups), stride,
-                                counts, status, ladders=self._ladders)
-                if (status != _lib.PILEUP_OK).any():
-                    k = int(np.nonzero(status != _lib.PILEUP_OK)[0][0])
-                    j = int(sel[k])
-                    raise _lib.TredGpuError("pileup: status {} for read {} of unit {}".format(
-                        int(status[k]), int(w.items[j] - b.unit_read_off[w.unit_of[j]]), int(w.unit_of[j])))
-                n_reads = np.bincount(gid[sel], minlength=len(groups))
-        for k, (g, a) in enumerate(groups):
-            prefix, repeat, suffix, _ = b.ladder_keys[g]
-            T = prefix + repeat * a + suffix
-            table = np.zeros((len(T) + 1, _lib.PILEUP_CHANNELS), np.int32)
-            if n_reads[k]:
-                table[:] = counts[k, :len(T) + 1]          # (a group with reads has a template of the ladder: it fits the stride)
-            out[g][a] = AlleleConsensus(a, n_reads[k], table, T, len(prefix), len(repeat))
-        return out
-
-    def _consensus_partial(self, w, alleles):
-        """consensus(partial=True): the groups have their shape from the alleles asked for, not from a read."""
-        from .consensus import AlleleConsensus
-        b = w.batch
-        group_of, groups, longest = {}, [], {}
-        for g, want in enumerate(alleles):
-            want = sorted(set(int(x) for x in want if int(x) >= 1))
-            for a in want:
-                group_of[(g, a)] = len(groups)
-                groups.append((g, a))
-            if want:
-                longest[g] = (want[-1], want[-2] if len(want) > 1 else 0)
+        groups, gid, anchor, n = place_consensus(w.tag, w.h, w.unit_of, alleles, partial)
         out = [{} for _ in range(b.n_units)]
         if not groups:
             return out
         ng = len(groups)
-        T_of = [len(b.ladder_keys[g][0]) + len(b.ladder_keys[g][1]) * a + len(b.ladder_keys[g][2]) for g, a in groups]
-        stride = max(T_of) + 1
-        n_full, n_part, n_amb, n_beyond = (np.zeros(ng, np.int64) for _ in range(4))
+        texts = [b.ladder_keys[g][0] + b.ladder_keys[g][1] * a + b.ladder_keys[g][2] for g, a in groups]
+        if partial:             # the groups have their shape from the alleles asked for, which may lie beyond the ladder
+            stride = max(len(T) for T in texts) + 1
+            tail = lambda sel: (np.ascontiguousarray(anchor[sel]), ng, self._group_ladders(b, groups),
+                                np.ascontiguousarray([a for _, a in groups], np.int32), stride, counts)
+        else:                   # ... from the ladder's templates: of the table the call is given, not the batch's own
+            stride = max(self.ctx._template_len(l) for l in self._ladders) + 1
+            tail = lambda sel: (ng, stride, counts)
         counts = np.zeros((ng, stride, _lib.PILEUP_CHANNELS), np.int32)
-        m_all = len(w.items)
-        gid, anchor = np.full(m_all, -1, np.int32), np.zeros(m_all, np.int32)
-        for j in range(m_all):
-            g, h, t = int(w.unit_of[j]), int(w.h[j]), int(w.tag[j])
-            if t == _lib.TAG_FULL:
-                k = group_of.get((g, h), -1)
-                if k >= 0:
-                    gid[j] = k
-                    n_full[k] += 1
-            elif t in (_lib.TAG_PREF, _lib.TAG_POST) and g in longest:
-                a_k, a_prev = longest[g]
-                k = group_of[(g, a_k)]
-                if h > a_k:
-                    n_beyond[k] += 1
-                elif h <= a_prev:
-                    n_amb[k] += 1
-                else:
-                    gid[j], anchor[j] = k, _lib.PILEUP_ANCHOR_BEGIN if t == _lib.TAG_PREF else _lib.PILEUP_ANCHOR_END
-                    n_part[k] += 1
-        sel = np.nonzero(gid >= 0)[0]
-        m = len(sel)
-        if m:
-            packed, woff, rlen = _gather_reads(w.packed, w.read_off, w.read_len, sel)
-            status = np.zeros(m, np.int32)
-            arr = lambda x, dt: np.ascontiguousarray(x[sel], dt)
-            reg = self._register(b.ladder_keys)
-            self.ctx.pileup_anchored(packed, woff, rlen, m, arr(w.item_ladder, np.int32), arr(w.win, np.int32),
-                                     arr(w.fields, np.int16), arr(w.ops, np.uint32), w.cap, arr(w.n_ops, np.int32),
-                                     arr(gid, np.int32), arr(anchor, np.int32), ng,
-                                     np.ascontiguousarray([reg[g] for g, _ in groups], np.int32),
-                                     np.ascontiguousarray([a for _, a in groups], np.int32), stride, counts, status,
-                                     ladders=self._ladders)
-            if (status != _lib.PILEUP_OK).any():
-                k = int(np.nonzero(status != _lib.PILEUP_OK)[0][0])
-                j = int(sel[k])
-                raise _lib.TredGpuError("pileup_anchored: status {} for read {} of unit {}".format(
-                    int(status[k]), int(w.items[j] - b.unit_read_off[w.unit_of[j]]), int(w.unit_of[j])))
-        for k, (g, a) in enumerate(groups):
-            prefix, repeat, suffix, _ = b.ladder_keys[g]
-            out[g][a] = AlleleConsensus(a, n_full[k], counts[k, :T_of[k] + 1], prefix + repeat * a + suffix, len(prefix),
-                                        len(repeat), partial=n_part[k], ambiguous=n_amb[k], beyond=n_beyond[k])
+        self._grouped("pileup_anchored" if partial else "pileup", w, gid, tail)
+        for k, ((g, a), T) in enumerate(zip(groups, texts)):
+            # (a template beyond the stride is beyond the ladder: nothing was counted on it)
+            table = counts[k] if len(T) < stride else np.zeros((len(T) + 1, _lib.PILEUP_CHANNELS), np.int32)
+            out[g][a] = AlleleConsensus(a, n["full"][k], table, T, len(b.ladder_keys[g][0]), len(b.ladder_keys[g][1]),
+                                        partial=n["partial"][k], ambiguous=n["ambiguous"][k], beyond=n["beyond"][k])
         return out
 
     # ---- which repeat units the reads of a locus show -------------------------------------------------
@@ -722,50 +716,21 @@ class Engine(object):
         for all units.  The classes of a unit: `full:a` for every a >= 1 of alleles[unit] (reads tagged FULL with h == a),
         `partial` (all PREF and POST reads, wherever consensus(partial=True) would lay them) and `rept` (all REPT reads);
         HANG reads are in none.  A unit whose period has no table (above _lib.SPECTRUM_MAX_PERIOD) comes back
-        `unsupported` and none of its reads are sent."""
+        `unsupported` and none of its reads are sent.  (The rule: place_spectrum.)"""
         from .spectrum import RepeatSpectrum
         w = self.winners(units) if winners is None else winners
         b = w.batch
-        group_of, groups = {}, []                                  # (unit, class name) -> group
-        for g in range(b.n_units):
-            if len(b.ladder_keys[g][1]) > _lib.SPECTRUM_MAX_PERIOD:
-                continue
-            want = sorted(set(int(x) for x in alleles[g] if int(x) >= 1))
-            for name in ["full:{}".format(a) for a in want] + ["partial", "rept"]:
-                group_of[(g, name)] = len(groups)
-                groups.append((g, name))
+        period = [len(k[1]) for k in b.ladder_keys]
+        groups, gid = place_spectrum(w.tag, w.h, w.unit_of, alleles, period)
         ng = len(groups)
         spec = np.zeros((ng, _lib.SPECTRUM_STRIDE), np.int32)
-        triples = [np.zeros((0, 3), np.int32)] * ng
-        m_all = len(w.items)
-        gid = np.full(m_all, -1, np.int32)
-        names = {_lib.TAG_PREF: "partial", _lib.TAG_POST: "partial", _lib.TAG_REPT: "rept"}
-        for j in range(m_all):
-            g, t = int(w.unit_of[j]), int(w.tag[j])
-            name = "full:{}".format(int(w.h[j])) if t == _lib.TAG_FULL else names.get(t)
-            gid[j] = group_of.get((g, name), -1)
-        sel = np.nonzero(gid >= 0)[0]
-        m = len(sel)
-        if m:
-            packed, woff, rlen = _gather_reads(w.packed, w.read_off, w.read_len, sel)
-            per_item, status = np.zeros((m, 3), np.int32), np.zeros(m, np.int32)
-            arr = lambda x, dt: np.ascontiguousarray(x[sel], dt)
-            reg = self._register(b.ladder_keys)
-            self.ctx.unit_spectrum(packed, woff, rlen, m, arr(w.item_ladder, np.int32), arr(w.win, np.int32),
-                                   arr(w.fields, np.int16), arr(w.ops, np.uint32), w.cap, arr(w.n_ops, np.int32),
-                                   arr(gid, np.int32), ng, np.ascontiguousarray([reg[g] for g, _ in groups], np.int32), spec,
-                                   per_item, status, ladders=self._ladders)
-            if (status != _lib.PILEUP_OK).any():
-                k = int(np.nonzero(status != _lib.PILEUP_OK)[0][0])
-                j = int(sel[k])
-                raise _lib.TredGpuError("unit_spectrum: status {} for read {} of unit {}".format(
-                    int(status[k]), int(w.items[j] - b.unit_read_off[w.unit_of[j]]), int(w.unit_of[j])))
-            by_group = np.argsort(gid[sel], kind="stable")
-            cut = np.searchsorted(gid[sel][by_group], np.arange(ng + 1))
-            triples = [per_item[by_group[cut[k]:cut[k + 1]]] for k in range(ng)]
-        tables = [None if len(b.ladder_keys[g][1]) > _lib.SPECTRUM_MAX_PERIOD else {} for g in range(b.n_units)]
+        per_item = np.zeros((len(gid), 3), np.int32)                # (the items sent fill its head)
+        sel = self._grouped("unit_spectrum", w, gid, lambda sel: (ng, self._group_ladders(b, groups), spec, per_item[:len(sel)]))
+        by_group = np.argsort(gid[sel], kind="stable")
+        cut = np.searchsorted(gid[sel][by_group], np.arange(ng + 1))
+        tables = [None if p > _lib.SPECTRUM_MAX_PERIOD else {} for p in period]
         for k, (g, name) in enumerate(groups):
-            tables[g][name] = (spec[k], triples[k])
+            tables[g][name] = (spec[k], per_item[by_group[cut[k]:cut[k + 1]]])
         return [RepeatSpectrum(b.ladder_keys[g][1], tables[g]) for g in range(b.n_units)]
 
     # ---- the whole path ------------------------------------------------------------------------------
@@ -804,6 +769,15 @@ def _batch(units):
 def _refuse_invalid(tag):
     if (tag == _lib.TAG_INVALID).any():
         raise _lib.TredGpuError("a read exceeds TREDGPU_MAX_READ_LEN")
+
+
+def _refuse_item(name, status, ok, items, unit_of, unit_read_off):
+    """Raises for the first item of a side call (items: the reads' indices in the batch) whose status is not `ok`."""
+    bad = np.nonzero(status != ok)[0]
+    if len(bad):
+        k = int(bad[0])
+        raise _lib.TredGpuError("{}: status {} for read {} of unit {}".format(name, int(status[k]), int(items[k] - unit_read_off[unit_of[k]]),
+                                                                          int(unit_of[k])))
 
 
 def _gather_reads(packed, read_off, read_len, reads):

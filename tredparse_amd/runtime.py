@@ -45,14 +45,27 @@ def timeline_dump():
             pass
 
 
+REPORTS = ("alignments", "consensus", "spectrum")     # the per-read reports, in the order their files are written
+_TAIL = ("alignments", "consensus", "consensus_partial", "spectrum")        # members 10-13 of a run() argument tuple
+
+
 def _options(arg):
-    """The reference's run() argument tuple, named; an eleventh member, where there is one, is --alignments, a twelfth
-    --consensus, a thirteenth --consensus-partial, a fourteenth --spectrum."""
+    """The reference's run() argument tuple, named.  Members 10-13, where the tuple has them (option_tail), are --alignments,
+    --consensus, --consensus-partial and --spectrum; `reports`: the REPORTS among them that are on, in that order."""
     samplekey, bam, repo, names, maxinsert, fullsearch, clip, alts, repeatpairs, log = arg[:10]
-    return dict(samplekey=samplekey, bam=bam, repo=repo, names=list(names), maxinsert=maxinsert,
-                fullsearch=fullsearch, clip=clip, alts=alts, repeatpairs=repeatpairs, log=log,
-                alignments=bool(arg[10]) if len(arg) > 10 else False, consensus=bool(arg[11]) if len(arg) > 11 else False,
-                consensus_partial=bool(arg[12]) if len(arg) > 12 else False, spectrum=bool(arg[13]) if len(arg) > 13 else False)
+    o = dict(samplekey=samplekey, bam=bam, repo=repo, names=list(names), maxinsert=maxinsert,
+             fullsearch=fullsearch, clip=clip, alts=alts, repeatpairs=repeatpairs, log=log)
+    for at, name in enumerate(_TAIL, 10):
+        o[name] = bool(arg[at]) if len(arg) > at else False
+    o["reports"] = [name for name in REPORTS if o[name]]
+    return o
+
+
+def option_tail(alignments=False, consensus=False, consensus_partial=False, spectrum=False):
+    """What follows the reference's ten members in a run() argument tuple for these flags, as _options reads it: nothing
+    when none is set."""
+    tail = (bool(alignments), bool(consensus), bool(consensus_partial), bool(spectrum))        # (in _TAIL's order)
+    return tail if any(tail) else ()
 
 
 def collect_sample(arg, long_reads=False):

@@ -37,7 +37,7 @@ from .models import GridError, SparseDist, format_call, pair_summaries
 
 logging.basicConfig()
 logger = logging.getLogger(__name__)
-from .runtime import TIMING, _options, collect_sample, mark, timeline_dump, timing_add                      # noqa: F401  (shared with feeder.py / emit.py)
+from .runtime import TIMING, _options, collect_sample, mark, option_tail, timeline_dump, timing_add                    # noqa: F401  (shared with feeder.py / emit.py)
 from .feeder import (_InflateFeeder, _plan_sample, _scan_planned, pinned_bytes,                # noqa: F401
                      release_inflaters)
 from .emit import Emitter                                                                  # noqa: F401
@@ -265,14 +265,10 @@ def _genotype(engine, picks, o):
             return
         br = engine.genotype_packed(batch, dense=True) if o["log"] == "DEBUG" else engine.genotype_packed(batch)
         br.repeatpairs = kw["repeatpairs"]
-        if o["alignments"] or o["consensus"] or o["spectrum"]:
-            winners = engine.winners(batch)                       # classify with the dump and the CIGAR call: once for all three
-            if o["alignments"]:
-                br.alignments = engine.alignments(batch, winners=winners)
-            if o["consensus"]:
-                br.consensus = engine.consensus(batch, _called_alleles(br), winners=winners, partial=o["consensus_partial"])
-            if o["spectrum"]:
-                br.spectrum = engine.spectrum(batch, _called_alleles(br), winners=winners)
+        if o["reports"]:
+            winners = engine.winners(batch)                       # classify with the dump and the CIGAR call: once for all reports
+            for name in o["reports"]:
+                setattr(br, name, REPORT_TABLE[name][1](engine, batch, br, winners, o))
         i = 0
         for si, _, ks in sub:
             if ks:
@@ -301,49 +297,55 @@ def _called_alleles(br):
     return [sorted({int(c["h1"]) // int(p), int(c["h2"]) // int(p)}) if int(c["status"]) == 0 else [] for c, p in zip(calls, period)]
 
 
-def consensus_text(scan, calls, res, partial=False):
+def _called(scan, calls, res):
+    """(k, name, UnitResult) of every locus that was called and has a result (res: {locus index: UnitResult})."""
+    for k, name in enumerate(scan.names):
+        r = res.get(k)
+        if r is not None and name + ".details" in calls:
+            yield k, name, r
+
+
+def consensus_text(scan, calls, res, o):
     """--consensus: {locus: {"alleles": [AlleleConsensus.to_dict(), ...]}} for every called locus, one entry per distinct
     called allele of at least one unit, smaller first; sorted keys.  res: {locus index: UnitResult with .consensus}.
-    partial (--consensus-partial): every allele with its `partial`, `ambiguous` and `beyond` counts."""
+    --consensus-partial: every allele with its `partial`, `ambiguous` and `beyond` counts."""
     out = {}
-    for k, name in enumerate(scan.names):
-        r = res.get(k)
-        if r is None or name + ".details" not in calls:
-            continue
+    for _, name, r in _called(scan, calls, res):
         alleles = sorted(set(int(a) for a in (calls[name + ".1"], calls[name + ".2"]) if int(a) >= 1))
-        out[name] = {"alleles": [r.consensus[a].to_dict(partial=partial) for a in alleles]}
+        out[name] = {"alleles": [r.consensus[a].to_dict(partial=o["consensus_partial"]) for a in alleles]}
     return json.dumps(out, sort_keys=True, indent=1) + "\n"
 
 
-def spectrum_text(scan, calls, res):
+def spectrum_text(scan, calls, res, o):
     """--spectrum: {locus: RepeatSpectrum.to_dict()} for every called locus; sorted keys.  res: {locus index: UnitResult
     with .spectrum}."""
-    out = {}
-    for k, name in enumerate(scan.names):
-        r = res.get(k)
-        if r is None or name + ".details" not in calls:
-            continue
-        out[name] = r.spectrum.to_dict()
-    return json.dumps(out, sort_keys=True, indent=1) + "\n"
+    return json.dumps({name: r.spectrum.to_dict() for _, name, r in _called(scan, calls, res)}, sort_keys=True, indent=1) + "\n"
 
 
-def alignments_text(scan, calls, res, repeatpairs):
+def alignments_text(scan, calls, res, o):
     """--alignments: for every `details` entry of every called locus, in `details` order, a header line
     `>{locus} {tag} h={h} {+|-} {read id}` (- : the template's reverse complement), the reference's verbose block for the
     pair (bam_parser.py:145-147) and a blank line.  res: {locus index: UnitResult with .alignments}."""
     from ._lib import TAG_NAMES
     out = []
-    for k, name in enumerate(scan.names):
-        r = res.get(k)
-        if r is None or name + ".details" not in calls:
-            continue
-        _, details, _ = tally(scan, k, r.tags, r.hs, repeatpairs=repeatpairs, lazy=True)
+    for k, name, r in _called(scan, calls, res):
+        _, details, _ = tally(scan, k, r.tags, r.hs, repeatpairs=o["repeatpairs"] or o["clip"], lazy=True)
         a, _ = scan.reads_of(k)
         for i, t, h in zip(details.reads.tolist(), details.tags.tolist(), details.hs.tolist()):
             x = r.alignments[i - a]
             assert (x.tag, x.h) == (t, h)
             out.append(">{} {} h={} {} {}\n{}\n".format(name, TAG_NAMES[t], h, "-" if x.strand else "+", scan.name(i), x.verbose()))
     return "".join(out)
+
+
+# report (runtime.REPORTS) -> (what follows <samplekey> in its file's name; compute(engine, batch, BatchResult, winners, o): the
+# BatchResult's member of that name; text(scan, calls, res, o): the file).  _genotype and Emitter._python_path loop over it.
+REPORT_TABLE = {
+    "alignments": (".alignments.txt", lambda e, b, br, w, o: e.alignments(b, winners=w), alignments_text),
+    "consensus": (".consensus.json", lambda e, b, br, w, o: e.consensus(b, _called_alleles(br), winners=w,
+                                                                        partial=o["consensus_partial"]), consensus_text),
+    "spectrum": (".spectrum.json", lambda e, b, br, w, o: e.spectrum(b, _called_alleles(br), winners=w), spectrum_text),
+}
 
 
 def genotype_scans(engine, task_args, scans):
@@ -363,7 +365,7 @@ def genotype_scans(engine, task_args, scans):
         o = _options(arg)
         # (a scan whose reads the device selected and still holds -- feeder._device_scan -- goes to the call that packs them there)
         on_device = getattr(pick[1], "device", None) is not None
-        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", o["alignments"], o["consensus"], o["consensus_partial"], o["spectrum"], on_device)
+        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", tuple(o["reports"]), o["consensus_partial"], on_device)
         groups.setdefault(key, (o, []))[1].append(pick)
     parts = {}
 
@@ -921,9 +923,8 @@ def main(args, quiet=False):
         if args.checkexists and not spawned:
             samples = [s for s in samples if not os.path.exists(s[0] + ".json")]
         tasks = [(key, bam, repo, [only] if only else loci, args.maxinsert, args.fullsearch, args.useclippedreads,
-                  not args.noalts, not args.norepeatpairs, args.log) + ((args.alignments, args.consensus) if args.alignments or args.consensus else ()) +
-                 ((args.consensus_partial,) if args.consensus_partial else ()) +
-                 ((False,) * (0 if args.consensus_partial else 1 if args.alignments or args.consensus else 3) + (True,) if args.spectrum else ())
+                  not args.noalts, not args.norepeatpairs, args.log) +
+                 option_tail(args.alignments, args.consensus, args.consensus_partial, args.spectrum)
                  for key, bam, only in samples]
         if not tasks:
             return
