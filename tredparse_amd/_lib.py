@@ -44,6 +44,10 @@ class Call(C.Structure):
                 ("lik", C.c_double), ("pp", C.c_double)]
 
 
+class TrioParams(C.Structure):
+    _fields_ = [("mu", C.c_double), ("rho", C.c_double), ("beta", C.c_double)]
+
+
 UNIT_DTYPE = np.dtype([("period", "<i4"), ("readlen", "<i4"), ("ploidy", "<i4"), ("maxinsert", "<i4"),
                        ("fullsearch", "<i4"), ("ref_len", "<i4"), ("minpe", "<i4"), ("cutoff_risk", "<i4"),
                        ("is_expansion", "<i4"), ("is_recessive", "<i4"), ("pe_off", "<i4"),
@@ -79,6 +83,16 @@ SPECTRUM_MAX_PERIOD = 6
 SPECTRUM_BINS = 4096            # 4^6 words, code = sum letter_i * 4^(p - 1 - i), A 0 C 1 G 2 T 3
 SPECTRUM_STRIDE = 4100          # the bins, then clean units, with_n, touched units, accepted items
 
+# the trio evaluation's symbols (include/tredtrio.h)
+TRIO_EXPORTS = ("tredtrio_evaluate", "tredtrio_get_timing", "tredtrio_reset_timing", "tredtrio_release", "tredtrio_last_error")
+TRIO_OK, TRIO_EMPTY_CHILD, TRIO_DEGENERATE, TRIO_TOO_LONG, TRIO_BAD_ITEM = 0, 1, 2, 4, 5
+TRIO_STATUS_NAMES = {TRIO_OK: "OK", TRIO_EMPTY_CHILD: "EMPTY_CHILD", TRIO_DEGENERATE: "DEGENERATE", TRIO_TOO_LONG: "TOO_LONG",
+                     TRIO_BAD_ITEM: "BAD_ITEM"}
+TRIO_MAX_ALLELE = 1024          # TREDGPU_TRIO_MAX_ALLELE: the largest allele of any pair list, in repeat units
+TRIO_PAIR_CHUNK = 1024          # TREDGPU_TRIO_PAIR_CHUNK: pairs of a parent's list staged in LDS at a time
+TRIO_GAMETE_TILE = 64           # TREDGPU_TRIO_GAMETE_TILE: distinct child alleles of one gamete workgroup
+TRIO_MU, TRIO_RHO, TRIO_BETA = 0.01, 0.9, 0.5      # the defaults of the transmission model: a choice, not a measurement
+
 # every symbol include/tredgpu.h declares (tests check the .so exports them all)
 EXPORTS = ("tredgpu_create", "tredgpu_destroy", "tredgpu_last_error", "tredgpu_sync", "tredgpu_get_stream",
            "tredgpu_version", "tredgpu_set_ladders", "tredgpu_set_model", "tredgpu_pack_reads",
@@ -96,6 +110,7 @@ KERNEL_CIGAR = 16               # include/tredcigar.h; tredgpu_get_timing's own 
 KERNEL_CIGAR_LONG = 17          # tredlong_cigar_timing (include/tredlong.h): a selector of the binding's only
 KERNEL_SECOND = 18              # tredsecond_get_timing (include/tredsecond.h): calls of sw_secondary and their device time
 KERNEL_PILEUP = 19              # tredpileup_get_timing (include/tredpileup.h): calls of pileup and their device time
+KERNEL_TRIO = 20                # tredtrio_get_timing (include/tredtrio.h): calls of trio and their device time
 
 
 # the timed opt-in units: (prefix, get-timing, reset-timing, KERNEL_* selector, last_error), in the order reset_timing has
@@ -105,7 +120,8 @@ KERNEL_PILEUP = 19              # tredpileup_get_timing (include/tredpileup.h): 
 SIDE_UNITS = (("tredlong", "tredlong_cigar_timing", "tredlong_cigar_reset_timing", KERNEL_CIGAR_LONG, "tredlong_last_error"),
               ("tredcigar", "tredcigar_get_timing", "tredcigar_reset_timing", KERNEL_CIGAR, "tredcigar_last_error"),
               ("tredsecond", "tredsecond_get_timing", "tredsecond_reset_timing", KERNEL_SECOND, "tredsecond_last_error"),
-              ("tredpileup", "tredpileup_get_timing", "tredpileup_reset_timing", KERNEL_PILEUP, "tredpileup_last_error"))
+              ("tredpileup", "tredpileup_get_timing", "tredpileup_reset_timing", KERNEL_PILEUP, "tredpileup_last_error"),
+              ("tredtrio", "tredtrio_get_timing", "tredtrio_reset_timing", KERNEL_TRIO, "tredtrio_last_error"))
 
 _lib = None
 
@@ -140,6 +156,7 @@ def load():
                                                vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
     lib.tredpileup_unit_spectrum.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                              vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
+    lib.tredtrio_evaluate.argtypes = [vp, C.POINTER(TrioParams), i64] + [vp] * 19
     for prefix, get_timing, reset_timing, _, last_error in SIDE_UNITS:
         getattr(lib, get_timing).argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
         getattr(lib, reset_timing).argtypes = [vp]
@@ -671,6 +688,20 @@ class Context:
         self._items_call("tredpileup_unit_spectrum", "tredpileup_last_error", ladders, packed, read_off, read_len, n_items,
                          item_ladder, item_template, _ptr(fields), _ptr(ops), cap, _ptr(n_ops), _ptr(item_group), n_groups,
                          _ptr(group_ladder), _ptr(out_spectrum), _ptr(out_item), _ptr(out_status))
+
+    def trio(self, n_items, child, father, mother, ploidy, father_informative, mother_informative, out_status, out_call,
+             out_values, out_J, mu=TRIO_MU, rho=TRIO_RHO, beta=TRIO_BETA):
+        """tredtrio_evaluate (include/tredtrio.h): n_items (trio, locus) items, host memory.  child, father, mother: the
+        members' pair lists as CSR tuples (off int64 [n + 1], a int32, b int32, lw float64), alleles in repeat units;
+        ploidy: int32 [n], the child's; father_informative / mother_informative: int32 [n], 0 for a parent that says
+        nothing.  out_status: int32 [n] (TRIO_*); out_call: int32 [n][3] (index in the child's list, a, b); out_values:
+        float64 [n][4] (Jmax, S, denovo, paternal); out_J: float64, parallel to the child's lists.  Parameters out of
+        range raise (-2), as every refusal of the call as a whole does."""
+        lists = [_ptr(x) for member in (child, father, mother) for x in member]
+        rc = self.lib.tredtrio_evaluate(self.h, C.byref(TrioParams(mu, rho, beta)), n_items, *lists, _ptr(ploidy),
+                                        _ptr(father_informative), _ptr(mother_informative), _ptr(out_status), _ptr(out_call),
+                                        _ptr(out_values), _ptr(out_J))
+        self._chk_side(rc, "tredtrio_evaluate failed ({})".format(rc), self.lib.tredtrio_last_error)
 
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")

@@ -733,6 +733,33 @@ class Engine(object):
             tables[g][name] = (spec[k], per_item[by_group[cut[k]:cut[k + 1]]])
         return [RepeatSpectrum(b.ladder_keys[g][1], tables[g]) for g in range(b.n_units)]
 
+    # ---- a child against its parents ------------------------------------------------------------------
+    def trio(self, children, fathers, mothers, ploidy, period=None, mu=_lib.TRIO_MU, rho=_lib.TRIO_RHO, beta=_lib.TRIO_BETA):
+        """Per item -- one (trio, locus) -- a trio.TrioResult: the child's call given what its parents could have passed on,
+        its posterior, the odds that an allele changed on the way (denovo) and that the larger allele is the father's
+        (paternal), in ONE Context.trio call for all items (the model: DESIGN.md 4, "Trio evaluation").  children, fathers,
+        mothers: per item a trio.PairList or a UnitResult with its dense grid (genotype_packed(b, dense=True); period: the
+        loci's periods then, one or per item); a parent that is None, was not called or has no pair says nothing.  ploidy:
+        the CHILD's, one or per item -- a ploidy-1 child ignores the father.  mu, rho, beta: the transmission model, whose
+        defaults are a choice, not a measurement.  Runs after the samples, not per read: no member of runtime.REPORTS.  An
+        item the unit refuses (TRIO_BAD_ITEM, TRIO_TOO_LONG) raises; a child without a pair comes back TRIO_EMPTY_CHILD."""
+        from .trio import PairList, TrioResult, member_list, pack_members
+        n = len(children)
+        if not (len(fathers) == len(mothers) == n):
+            raise ValueError("children, fathers and mothers must be of one length")
+        per = np.broadcast_to(np.asarray(0 if period is None else period, np.int64), (n,))
+        lists = [[member_list(x, int(p) or None) for x, p in zip(role, per)] for role in (children, fathers, mothers)]
+        kids = [k if k is not None else PairList([], [], []) for k in lists[0]]
+        (child, _), (father, f_inf), (mother, m_inf) = (pack_members(x) for x in [kids] + lists[1:])
+        status, call, values = np.zeros(n, np.int32), np.zeros((n, 3), np.int32), np.zeros((n, 4), np.float64)
+        J = np.zeros(int(child[0][-1]), np.float64)
+        if n:
+            self.ctx.trio(n, child, father, mother, np.ascontiguousarray(np.broadcast_to(np.asarray(ploidy, np.int32), (n,))),
+                          f_inf, m_inf, status, call, values, J, mu=mu, rho=rho, beta=beta)
+        refused = np.where((status == _lib.TRIO_BAD_ITEM) | (status == _lib.TRIO_TOO_LONG), status, _lib.TRIO_OK)
+        _refuse_item("trio", refused, _lib.TRIO_OK, np.zeros(n, np.int64), np.arange(n), np.zeros(n, np.int64))
+        return [TrioResult(status[i], call[i], values[i], J[child[0][i]:child[0][i + 1]], kids[i]) for i in range(n)]
+
     # ---- the whole path ------------------------------------------------------------------------------
     def genotype(self, units, want_grid=True):
         """SW + tagging -> histograms -> likelihood grid for a batch of units (a list of Unit, or a PackedUnits); returns

@@ -41,6 +41,7 @@ from .runtime import TIMING, _options, collect_sample, mark, option_tail, timeli
 from .feeder import (_InflateFeeder, _plan_sample, _scan_planned, pinned_bytes,                # noqa: F401
                      release_inflaters)
 from .emit import Emitter                                                                  # noqa: F401
+from .trio import add_model_options, run_pedigree
 
 
 # (ID, Number, Type, Description) of the VCF meta lines, in file order
@@ -104,6 +105,12 @@ def set_argparse():
                    help="also write <samplekey>.spectrum.json: per called locus which repeat-unit words (CAG, CAA, CCG, ...) its "
                         "reads show and how often -- the spanning, the partial and the in-repeat reads apart -- and how pure "
                         "the tract is")
+    p.add_argument("--pedigree",
+                   help="PED file (family, sample key, father, mother, sex, phenotype; 0 for a missing parent): once every "
+                        "sample's files are written, also write <childkey>.trio.json for every child of it -- the call given "
+                        "what the parents could have passed on, its posterior, and the odds that an allele changed on the way "
+                        "(python -m tredparse_amd.trio runs the same pass over the files of a --workdir)")
+    add_model_options(p, prefix="trio-")
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     p.add_argument("--toy", action="store_true", help=argparse.SUPPRESS)
     g = p.add_argument_group("Performance options")
@@ -877,10 +884,30 @@ def plan_drivers(args, n_samples, usable):
     return per_gpu, args.cpus or threads
 
 
+def _pedigree_pass(args, pedigree, repo, loci, engine=None):
+    """--pedigree: the trio pass over the files of the working directory (the current one), in this process -- on the
+    run's own engine where this process has one, else (the samples went to --gpus children, which have ended) on one of
+    its own on --gpu."""
+    own = engine is None
+    if own:
+        from .engine import Engine
+        engine = Engine(args.gpu)
+    try:
+        for path in run_pedigree(pedigree, ".", engine, repo, loci=loci, mu=args.trio_mu, rho=args.trio_rho, beta=args.trio_beta):
+            logger.info("wrote %s", path)
+    finally:
+        if own:
+            engine.close()
+
+
 def main(args, quiet=False):
     argv = list(args)
     p = set_argparse()
     args = p.parse_args(argv)
+    if args.pedigree and args.no_output:
+        p.error("--pedigree reads the samples' files: it cannot go with --no-output")
+    # (a --gpus child leaves the pass to the process that started it; the path is taken before the working directory changes)
+    pedigree = os.path.abspath(args.pedigree) if args.pedigree and not args.task_file else None
     quiet = quiet or args.quiet_json
     from . import shard
     usable = shard.usable_cpus()               # (of the inherited mask: what the whole job has, before this rank is pinned)
@@ -927,8 +954,11 @@ def main(args, quiet=False):
                  option_tail(args.alignments, args.consensus, args.consensus_partial, args.spectrum)
                  for key, bam, only in samples]
         if not tasks:
+            if pedigree:
+                _pedigree_pass(args, pedigree, repo, loci)
             return
         drivers = 1
+        engine = None
         if not spawned:
             drivers, args.cpus = plan_drivers(args, len(tasks), usable)
         if args.gpus * drivers > 1 and not spawned:
@@ -976,6 +1006,8 @@ def main(args, quiet=False):
                         engine.close()
                         mark("engine closed")
                     timeline_dump()
+        if pedigree:          # every sample's files are written (the emitter is closed, the --gpus children have ended)
+            _pedigree_pass(args, pedigree, repo, loci, engine=engine)
         print("Elapsed time={}".format(timedelta(seconds=time.time() - t0)), file=sys.stderr)
     finally:
         os.chdir(cwd)
