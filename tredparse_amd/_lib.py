@@ -48,6 +48,10 @@ class TrioParams(C.Structure):
     _fields_ = [("mu", C.c_double), ("rho", C.c_double), ("beta", C.c_double)]
 
 
+class CohortParams(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("alpha", C.c_double)]
+
+
 UNIT_DTYPE = np.dtype([("period", "<i4"), ("readlen", "<i4"), ("ploidy", "<i4"), ("maxinsert", "<i4"),
                        ("fullsearch", "<i4"), ("ref_len", "<i4"), ("minpe", "<i4"), ("cutoff_risk", "<i4"),
                        ("is_expansion", "<i4"), ("is_recessive", "<i4"), ("pe_off", "<i4"),
@@ -93,6 +97,17 @@ TRIO_PAIR_CHUNK = 1024          # TREDGPU_TRIO_PAIR_CHUNK: pairs of a parent's l
 TRIO_GAMETE_TILE = 64           # TREDGPU_TRIO_GAMETE_TILE: distinct child alleles of one gamete workgroup
 TRIO_MU, TRIO_RHO, TRIO_BETA = 0.01, 0.9, 0.5      # the defaults of the transmission model: a choice, not a measurement
 
+# the cohort frequencies' symbols (include/tredcohort.h)
+COHORT_EXPORTS = ("tredcohort_evaluate", "tredcohort_get_timing", "tredcohort_reset_timing", "tredcohort_release",
+                  "tredcohort_last_error")
+COHORT_OK, COHORT_EMPTY, COHORT_TOO_LONG, COHORT_BAD_ITEM = 0, 1, 4, 5
+COHORT_STATUS_NAMES = {COHORT_OK: "OK", COHORT_EMPTY: "EMPTY", COHORT_TOO_LONG: "TOO_LONG", COHORT_BAD_ITEM: "BAD_ITEM"}
+COHORT_MAX_ALLELE = 1024        # TREDGPU_COHORT_MAX_ALLELE: the largest allele of any pair list, in repeat units
+COHORT_MAX_ITERS = 4096         # TREDGPU_COHORT_MAX_ITERS
+COHORT_CHUNK = 1024             # TREDGPU_COHORT_CHUNK: incidence entries of an allele one wavefront sums in the M-step
+COHORT_LONG_LIST = 1024         # TREDGPU_COHORT_LONG_LIST: a sample of more pairs has a workgroup to itself, any other a wavefront
+COHORT_ITERS, COHORT_ALPHA, COHORT_TOL = 64, 1.0, 1e-6     # EM iterations, pseudo-chromosomes, what `converged` reports: a choice
+
 # every symbol include/tredgpu.h declares (tests check the .so exports them all)
 EXPORTS = ("tredgpu_create", "tredgpu_destroy", "tredgpu_last_error", "tredgpu_sync", "tredgpu_get_stream",
            "tredgpu_version", "tredgpu_set_ladders", "tredgpu_set_model", "tredgpu_pack_reads",
@@ -111,6 +126,7 @@ KERNEL_CIGAR_LONG = 17          # tredlong_cigar_timing (include/tredlong.h): a 
 KERNEL_SECOND = 18              # tredsecond_get_timing (include/tredsecond.h): calls of sw_secondary and their device time
 KERNEL_PILEUP = 19              # tredpileup_get_timing (include/tredpileup.h): calls of pileup and their device time
 KERNEL_TRIO = 20                # tredtrio_get_timing (include/tredtrio.h): calls of trio and their device time
+KERNEL_COHORT = 21              # tredcohort_get_timing (include/tredcohort.h): calls of cohort and their device time
 
 
 # the timed opt-in units: (prefix, get-timing, reset-timing, KERNEL_* selector, last_error), in the order reset_timing has
@@ -121,7 +137,8 @@ SIDE_UNITS = (("tredlong", "tredlong_cigar_timing", "tredlong_cigar_reset_timing
               ("tredcigar", "tredcigar_get_timing", "tredcigar_reset_timing", KERNEL_CIGAR, "tredcigar_last_error"),
               ("tredsecond", "tredsecond_get_timing", "tredsecond_reset_timing", KERNEL_SECOND, "tredsecond_last_error"),
               ("tredpileup", "tredpileup_get_timing", "tredpileup_reset_timing", KERNEL_PILEUP, "tredpileup_last_error"),
-              ("tredtrio", "tredtrio_get_timing", "tredtrio_reset_timing", KERNEL_TRIO, "tredtrio_last_error"))
+              ("tredtrio", "tredtrio_get_timing", "tredtrio_reset_timing", KERNEL_TRIO, "tredtrio_last_error"),
+              ("tredcohort", "tredcohort_get_timing", "tredcohort_reset_timing", KERNEL_COHORT, "tredcohort_last_error"))
 
 _lib = None
 
@@ -157,6 +174,7 @@ def load():
     lib.tredpileup_unit_spectrum.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                              vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.tredtrio_evaluate.argtypes = [vp, C.POINTER(TrioParams), i64] + [vp] * 19
+    lib.tredcohort_evaluate.argtypes = [vp, C.POINTER(CohortParams), i64] + [vp] * 16
     for prefix, get_timing, reset_timing, _, last_error in SIDE_UNITS:
         getattr(lib, get_timing).argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
         getattr(lib, reset_timing).argtypes = [vp]
@@ -702,6 +720,21 @@ class Context:
                                         _ptr(father_informative), _ptr(mother_informative), _ptr(out_status), _ptr(out_call),
                                         _ptr(out_values), _ptr(out_J))
         self._chk_side(rc, "tredtrio_evaluate failed ({})".format(rc), self.lib.tredtrio_last_error)
+
+    def cohort(self, n_items, item_off, samples, ploidy, allele_off, out_status, out_n_alleles, out_alleles, out_freq, out_count,
+               out_trace, out_sample_call, out_sample_values, out_r, iters=COHORT_ITERS, alpha=COHORT_ALPHA):
+        """tredcohort_evaluate (include/tredcohort.h): n_items items -- one locus with its samples each --, host memory.
+        item_off: int64 [n + 1], the samples of an item; samples: their pair lists as one CSR tuple (off int64
+        [n_samples + 1], a int32, b int32, lw float64), alleles in repeat units; ploidy: int32 [n_samples]; allele_off: int64
+        [n + 1], the room of an item in out_alleles (int32), out_freq and out_count (float64).  out_status, out_n_alleles:
+        int32 [n]; out_trace: float64 [n][iters][2]; out_sample_call: int32 [n_samples][3] (index in the sample's list, a,
+        b); out_sample_values: float64 [n_samples][2] (logZ, post); out_r: float64, parallel to the pairs.  Parameters out
+        of range raise (-2), as every refusal of the call as a whole does."""
+        rc = self.lib.tredcohort_evaluate(self.h, C.byref(CohortParams(int(iters), float(alpha))), n_items, _ptr(item_off),
+                                          *(_ptr(x) for x in samples), _ptr(ploidy), _ptr(allele_off), _ptr(out_status),
+                                          _ptr(out_n_alleles), _ptr(out_alleles), _ptr(out_freq), _ptr(out_count), _ptr(out_trace),
+                                          _ptr(out_sample_call), _ptr(out_sample_values), _ptr(out_r))
+        self._chk_side(rc, "tredcohort_evaluate failed ({})".format(rc), self.lib.tredcohort_last_error)
 
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")

@@ -760,6 +760,32 @@ class Engine(object):
         _refuse_item("trio", refused, _lib.TRIO_OK, np.zeros(n, np.int64), np.arange(n), np.zeros(n, np.int64))
         return [TrioResult(status[i], call[i], values[i], J[child[0][i]:child[0][i + 1]], kids[i]) for i in range(n)]
 
+    # ---- all samples of a locus ----------------------------------------------------------------------
+    def cohort(self, lists_per_locus, ploidy_per_locus, period=None, iters=_lib.COHORT_ITERS, alpha=_lib.COHORT_ALPHA,
+               tol=_lib.COHORT_TOL):
+        """Per locus a cohort.CohortResult: the allele frequencies of the locus by EM over the (h1, h2) surfaces of all its
+        samples, and per sample the call under those frequencies as a Hardy-Weinberg prior, its posterior over its pairs
+        and logZ, in ONE Context.cohort call for all loci (the model: DESIGN.md 4, "Cohort frequencies").
+        lists_per_locus: per locus, per sample a trio.PairList or a UnitResult with its dense grid (genotype_packed(b,
+        dense=True); period: the loci's periods then, one or per locus); a sample that is None, was not called or has no
+        pair takes no part.  ploidy_per_locus: per locus one ploidy or one per sample.  iters, alpha: the EM's iterations,
+        all of which run, and the pseudo-chromosomes; tol: what `converged` reports against -- a choice, not a measurement.
+        Runs after the samples, not per read: no member of runtime.REPORTS.  A locus the unit refuses (COHORT_BAD_ITEM,
+        COHORT_TOO_LONG) raises; one without a participating sample comes back COHORT_EMPTY."""
+        from .cohort import cohort_outputs, pack_cohort, results_of
+        from .trio import member_list
+        n = len(lists_per_locus)
+        per = np.broadcast_to(np.asarray(0 if period is None else period, np.int64), (n,))
+        lists = [[member_list(x, int(p) or None) for x in locus] for locus, p in zip(lists_per_locus, per)]
+        item_off, samples, ploidy, allele_off, members = pack_cohort(lists, ploidy_per_locus)
+        out = cohort_outputs(n, len(members), int(samples[0][-1]), int(allele_off[-1]), int(iters))
+        if n:
+            self.ctx.cohort(n, item_off, samples, ploidy, allele_off, *out, iters=iters, alpha=alpha)
+        status = out[0]
+        refused = np.where((status == _lib.COHORT_BAD_ITEM) | (status == _lib.COHORT_TOO_LONG), status, _lib.COHORT_OK)
+        _refuse_item("cohort", refused, _lib.COHORT_OK, np.zeros(n, np.int64), np.arange(n), np.zeros(n, np.int64))
+        return results_of(n, item_off, samples, ploidy, allele_off, members, out, tol)
+
     # ---- the whole path ------------------------------------------------------------------------------
     def genotype(self, units, want_grid=True):
         """SW + tagging -> histograms -> likelihood grid for a batch of units (a list of Unit, or a PackedUnits); returns

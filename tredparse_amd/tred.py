@@ -42,6 +42,7 @@ from .feeder import (_InflateFeeder, _plan_sample, _scan_planned, pinned_bytes, 
                      release_inflaters)
 from .emit import Emitter                                                                  # noqa: F401
 from .trio import add_model_options, run_pedigree
+from .cohort import add_model_options as add_cohort_options, run_cohort
 
 
 # (ID, Number, Type, Description) of the VCF meta lines, in file order
@@ -111,6 +112,12 @@ def set_argparse():
                         "what the parents could have passed on, its posterior, and the odds that an allele changed on the way "
                         "(python -m tredparse_amd.trio runs the same pass over the files of a --workdir)")
     add_model_options(p, prefix="trio-")
+    p.add_argument("--cohort", action="store_true",
+                   help="once every sample's files are written, also write cohort.json and cohort.calls.tsv: per locus the allele "
+                        "frequencies estimated by EM from all samples' (h1, h2) surfaces and posterior-weighted risk, pre-risk "
+                        "and carrier counts, per sample the call under those frequencies (python -m tredparse_amd.cohort runs "
+                        "the same pass over the files of a run)")
+    add_cohort_options(p, prefix="cohort-")
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     p.add_argument("--toy", action="store_true", help=argparse.SUPPRESS)
     g = p.add_argument_group("Performance options")
@@ -900,6 +907,29 @@ def _pedigree_pass(args, pedigree, repo, loci, engine=None):
             engine.close()
 
 
+def _cohort_pass(args, keys, repo, loci, engine=None):
+    """--cohort: the cohort pass over the samples' files in the working directory (the current one), in this process -- on
+    the run's own engine where this process has one, else (the samples went to --gpus children, which have ended) on one of
+    its own on --gpu."""
+    files = []
+    for key in keys:
+        if os.path.exists(key + ".json"):
+            files.append(key + ".json")
+        else:
+            logger.warning("sample `%s` has no %s.json: it takes no part in the cohort", key, key)
+    own = engine is None
+    if own:
+        from .engine import Engine
+        engine = Engine(args.gpu)
+    try:
+        for path in run_cohort(files, "cohort", engine, repo, loci=loci, iters=args.cohort_iters, alpha=args.cohort_alpha,
+                               tol=args.cohort_tol):
+            logger.info("wrote %s", path)
+    finally:
+        if own:
+            engine.close()
+
+
 def main(args, quiet=False):
     argv = list(args)
     p = set_argparse()
@@ -908,6 +938,9 @@ def main(args, quiet=False):
         p.error("--pedigree reads the samples' files: it cannot go with --no-output")
     # (a --gpus child leaves the pass to the process that started it; the path is taken before the working directory changes)
     pedigree = os.path.abspath(args.pedigree) if args.pedigree and not args.task_file else None
+    if args.cohort and args.no_output:
+        p.error("--cohort reads the samples' files: it cannot go with --no-output")
+    cohort = args.cohort and not args.task_file
     quiet = quiet or args.quiet_json
     from . import shard
     usable = shard.usable_cpus()               # (of the inherited mask: what the whole job has, before this rank is pinned)
@@ -947,6 +980,7 @@ def main(args, quiet=False):
         repo.set_ploidy(args.haploid)
         loci = ["HD"] if args.toy else (args.tred or repo.names)
         spawned = bool(args.task_file)
+        keys = list(dict.fromkeys(s[0] for s in samples))          # (--cohort: every sample, those --checkexists skips too)
         if args.checkexists and not spawned:
             samples = [s for s in samples if not os.path.exists(s[0] + ".json")]
         tasks = [(key, bam, repo, [only] if only else loci, args.maxinsert, args.fullsearch, args.useclippedreads,
@@ -956,6 +990,8 @@ def main(args, quiet=False):
         if not tasks:
             if pedigree:
                 _pedigree_pass(args, pedigree, repo, loci)
+            if cohort:
+                _cohort_pass(args, keys, repo, loci)
             return
         drivers = 1
         engine = None
@@ -1008,6 +1044,8 @@ def main(args, quiet=False):
                     timeline_dump()
         if pedigree:          # every sample's files are written (the emitter is closed, the --gpus children have ended)
             _pedigree_pass(args, pedigree, repo, loci, engine=engine)
+        if cohort:
+            _cohort_pass(args, keys, repo, loci, engine=engine)
         print("Elapsed time={}".format(timedelta(seconds=time.time() - t0)), file=sys.stderr)
     finally:
         os.chdir(cwd)
