@@ -111,13 +111,60 @@ __device__ __forceinline__ int row_excl_scan_max(int x) {
     return dpp_row_shr<0x111>(NEG, x);
 }
 
-// max over the 16 lanes of a DPP row, delivered to every lane of the row: four rotate-and-max steps
+// max over the 16 lanes of a DPP row, delivered to every lane of the row: four rotate-and-max steps.  (A rotation gives
+// every lane a source, so `old` is never seen; written as the identity of max the compiler folds move and max into one
+// v_max_i32_dpp per step, as in row_excl_scan_max -- with old = x it emitted v_mov, s_nop, v_mov_dpp, v_max.)
 __device__ __forceinline__ int row_max_all(int x) {
-    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x121, 0xF, 0xF, false));   // row_ror:1
-    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x122, 0xF, 0xF, false));   // row_ror:2
-    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x124, 0xF, 0xF, false));   // row_ror:4
-    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x128, 0xF, 0xF, false));   // row_ror:8
+    constexpr int IMIN = -2147483647 - 1;
+    x = max(x, __builtin_amdgcn_update_dpp(IMIN, x, 0x121, 0xF, 0xF, false));   // row_ror:1
+    x = max(x, __builtin_amdgcn_update_dpp(IMIN, x, 0x122, 0xF, 0xF, false));   // row_ror:2
+    x = max(x, __builtin_amdgcn_update_dpp(IMIN, x, 0x124, 0xF, 0xF, false));   // row_ror:4
+    x = max(x, __builtin_amdgcn_update_dpp(IMIN, x, 0x128, 0xF, 0xF, false));   // row_ror:8
     return x;
+}
+
+// inclusive max scan over the 16 lanes of a DPP row, one fused v_max_i32_dpp per step (old = the identity of max:
+// a lane without a source keeps its own value, exactly as row_scan_max's old = x)
+__device__ __forceinline__ int row_scan_max_fused(int x) {
+    constexpr int IMIN = -2147483647 - 1;
+    x = max(x, dpp_row_shr<0x111>(IMIN, x));
+    x = max(x, dpp_row_shr<0x112>(IMIN, x));
+    x = max(x, dpp_row_shr<0x114>(IMIN, x));
+    x = max(x, dpp_row_shr<0x118>(IMIN, x));
+    return x;
+}
+
+// row_excl_scan_max(run) with the column's E~ updates E[r] = max(E[r], q[r]), r < 10, in the scan's wait states.  A DPP
+// operand must have been written two instructions earlier; the scan's five steps depend on each other, and what the
+// compiler finds to put between them (the four instructions of the reach test) leaves five wait states of s_nop in every
+// column, while the E~ updates -- which need nothing from the scan -- end up behind it.  One asm block, so that the
+// order holds: two updates in front of every step (the first pair covers the write of `run`, whatever wrote it).
+// `before` is not used: a value the column has to have computed by now (the reach test's operand, the last reader of
+// `run` besides the scan -- so that the scan takes over run's register instead of a copy).
+// The first lane of a row gets 0 (bound_ctrl) where row_excl_scan_max gives NEG, which saves loading NEG in every
+// column; the same to the caller, whose max3 holds a value >= Z(row, col) > 0 (sweep_column).
+__device__ __forceinline__ int row_excl_scan_max_e10(int x, int* E, const int* q, int before) {
+    int fin;
+    asm("v_max_i32 %2, %2, %12\n\t"
+        "v_max_i32 %3, %3, %13\n\t"
+        "v_max_i32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32 %4, %4, %14\n\t"
+        "v_max_i32 %5, %5, %15\n\t"
+        "v_max_i32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32 %6, %6, %16\n\t"
+        "v_max_i32 %7, %7, %17\n\t"
+        "v_max_i32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32 %8, %8, %18\n\t"
+        "v_max_i32 %9, %9, %19\n\t"
+        "v_max_i32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32 %10, %10, %20\n\t"
+        "v_max_i32 %11, %11, %21\n\t"
+        "v_mov_b32_dpp %1, %0 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "+v"(x), "=v"(fin), "+v"(E[0]), "+v"(E[1]), "+v"(E[2]), "+v"(E[3]), "+v"(E[4]), "+v"(E[5]), "+v"(E[6]),
+          "+v"(E[7]), "+v"(E[8]), "+v"(E[9])
+        : "v"(q[0]), "v"(q[1]), "v"(q[2]), "v"(q[3]), "v"(q[4]), "v"(q[5]), "v"(q[6]), "v"(q[7]), "v"(q[8]), "v"(q[9]),
+          "v"(before));
+    return fin;
 }
 
 // One DP column for all rows of the four alignments in this wave; LET = template letter (4 = N).
@@ -147,6 +194,8 @@ __device__ __forceinline__ void sweep_column(const Rows<R>& J, const int (&SL)[R
     // last row of the lane above, previous column; above the first row lies Z(-1, col-1) = (col << 9) + (col-2)*geK
     const int hup = __builtin_amdgcn_update_dpp((col << 9) + s_scale - 2 * geK, H[R - 1], 0x111, 0xF, 0xF, false);
     int ht[R], pl[R];
+    constexpr int RQ = R >= 10 ? 10 : 0;   // rows whose E~ update waits for the scan (row_excl_scan_max_e10)
+    int qd[RQ > 0 ? RQ : 1];
     int diag = hup;
     int run = NEG;
 #pragma unroll
@@ -163,10 +212,15 @@ __device__ __forceinline__ void sweep_column(const Rows<R>& J, const int (&SL)[R
         // E~ for the next column.  Fed from H without the vertical-gap term: a vertical gap followed by
         // a horizontal one has an equal-score twin (horizontal, then vertical) with the same end points
         // that the F recurrence does admit, so nothing is lost (ssw.c:238 makes the same choice).
-        E[r] = max(E[r], q);
+        if (r < RQ) qd[r] = q;
+        else E[r] = max(E[r], q);
     }
     // exclusive max scan across the 16 lanes: F~ entering this lane from the lanes above
-    const int fin = row_excl_scan_max(run);
+    constexpr int MID = R / 2;
+    const int reach = max(pl[MID], run - MID * geK);   // (see the reach test below)
+    int fin;
+    if constexpr (RQ > 0) fin = row_excl_scan_max_e10(run, E, qd, reach);
+    else fin = row_excl_scan_max(run);
 #pragma unroll
     for (int r = 0; r < R; ++r) H[r] = max3(ht[r], pl[r], fin);
     // running best: only columns in which some lane could beat its best take the exact path.
@@ -175,9 +229,8 @@ __device__ __forceinline__ void sweep_column(const Rows<R>& J, const int (&SL)[R
     // Two segments: rows below MID over-estimate by < MID*ge, the others by <= (R-1-MID)*ge (pl[MID] is the maximum of
     // the rows above MID).  With one segment the slack was (R-1)*ge = 18 at the default scoring -- more than the 11 a
     // one-period gap costs, so on a periodic trunk nearly every lane was "within reach" in nearly every column.
-    constexpr int MID = R / 2;
     const int lane_scale = row0g + s_scale;
-    const bool trig = max(pl[MID], run - MID * geK) + c0 - lane_scale > T.ceil;
+    const bool trig = reach + c0 - lane_scale > T.ceil;
     if (__builtin_amdgcn_ballot_w64(trig) != 0) {
         // exact: does some row of this lane score more than the lane's best?  (a later column never wins a tie)
         int tr[R];
@@ -204,6 +257,11 @@ __device__ __forceinline__ void sweep_column(const Rows<R>& J, const int (&SL)[R
     }
 }
 
+// Rows of a template end whose LDS values are fetched in one batch (combine, resolve_best): all of them where the
+// registers of the column's temporaries hold them, half of them in the instantiations that already spill.
+template <int R>
+constexpr int END_CHUNK = R == 7 ? 4 : R <= 10 ? R : (R + 1) / 2 > 10 ? 8 : (R + 1) / 2;
+
 // Turns the note left by sweep_column into the lane's best cell: the row is the maximum of score<<18 | (R-1-r) over
 // the parked rows (smallest row among equal scores), the start payload that row's packed value.  Wave-uniform call.
 template <int R>
@@ -212,8 +270,17 @@ __device__ __forceinline__ void resolve_best(Track& T, int row0, int row0g, int 
     if (__builtin_amdgcn_ballot_w64(pend) == 0) return;
     const int pcol = -1 - T.bestkey;     // (lanes without a note compute on stale rows and keep what they have)
     int m = NEG;
+    // (the parked rows are read END_CHUNK at a time, all reads of a chunk in front of its arithmetic: one LDS round trip
+    //  per chunk -- left to itself the compiler waits for every pair of rows before it asks for the next)
 #pragma unroll
-    for (int r = 0; r < R; ++r) m = max(m, (rowbuf[r * 64] & ~PAYMASK) | (R - 1 - r));
+    for (int r0 = 0; r0 < R; r0 += END_CHUNK<R>) {
+        int pr[END_CHUNK<R>];
+#pragma unroll
+        for (int k = 0; k < END_CHUNK<R>; ++k) if (r0 + k < R) pr[k] = rowbuf[(r0 + k) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < END_CHUNK<R>; ++k) if (r0 + k < R) m = max(m, (pr[k] & ~PAYMASK) | (R - 1 - (r0 + k)));
+    }
     static_assert(R <= 32, "row index in five payload bits");
     const int st = rowbuf[(R - 1 - (m & 31)) * 64];
     const int lane_scale = row0g + pcol * geK;
@@ -651,13 +718,24 @@ __global__ __launch_bounds__(64, W) void sw_cont_kernel(SwArgs a) {
                 // behind it the start payload the candidate carries.  The lane's largest (key, payload) pair is taken
                 // by 64-bit max atomics on a slot of the lane's own in LDS: the 2R compare-and-keep steps cost no VALU
                 // issue slot (a second pass over the rows to find the winner's payload cost as much as the first).
+                // The continuation values are read END_CHUNK rows at a time, all reads of a chunk in front of its first
+                // atomic: the compiler may not move a read across an atomic that might alias it, and with read, key and
+                // atomics row by row every row waited for its own LDS round trip (and for the previous row's atomics).
                 long long* const slot = reinterpret_cast<long long*>(wbuf + (3 * R + 2) * PS) + lane_now();
-                *slot = (long long)NEG * (1LL << 32);
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const int sh = (H[r] & ~PAYMASK) + wb[r * PS], se = (E[r] & ~PAYMASK) + wb[(R + r) * PS];
-                    atomicMax(slot, (long long)(((unsigned long long)(uint32_t)sh << 32) | (uint32_t)(H[r] & PAYMASK)));
-                    atomicMax(slot, (long long)(((unsigned long long)(uint32_t)se << 32) | (uint32_t)(E[r] & PAYMASK)));
+                for (int r0 = 0; r0 < R; r0 += END_CHUNK<R>) {
+                    int wh[END_CHUNK<R>], we[END_CHUNK<R>];
+#pragma unroll
+                    for (int k = 0; k < END_CHUNK<R>; ++k)
+                        if (r0 + k < R) { wh[k] = wb[(r0 + k) * PS]; we[k] = wb[(R + r0 + k) * PS]; }
+                    if (r0 == 0) *slot = (long long)NEG * (1LL << 32);
+#pragma unroll
+                    for (int k = 0; k < END_CHUNK<R>; ++k) if (r0 + k < R) {
+                        const int r = r0 + k;
+                        const int sh = (H[r] & ~PAYMASK) + wh[k], se = (E[r] & ~PAYMASK) + we[k];
+                        atomicMax(slot, (long long)(((unsigned long long)(uint32_t)sh << 32) | (uint32_t)(H[r] & PAYMASK)));
+                        atomicMax(slot, (long long)(((unsigned long long)(uint32_t)se << 32) | (uint32_t)(E[r] & PAYMASK)));
+                    }
                 }
                 const long long won = *slot;
                 int m = (int)(won >> 32);
@@ -668,11 +746,7 @@ __global__ __launch_bounds__(64, W) void sw_cont_kernel(SwArgs a) {
                 if (!full_dump) {
                     // the template's exact score is known now (T.ceil carries the trunk's best score): drop it unless
                     // it can pass the score filter and beat the arg-max of some read
-                    int ks = max(m, T.ceil);
-                    ks = max(ks, dpp_row_shr<0x111>(ks, ks));
-                    ks = max(ks, dpp_row_shr<0x112>(ks, ks));
-                    ks = max(ks, dpp_row_shr<0x114>(ks, ks));
-                    ks = max(ks, dpp_row_shr<0x118>(ks, ks));
+                    int ks = row_scan_max_fused(max(m, T.ceil));
                     if (with_sfx) ks = max(ks, wb[(2 * R) * PS]);   // (its column shift does not touch the score)
                     const int bestS = best >> 12, bestU = 511 - ((best >> 3) & 511);
                     const int need_score = max(max(min(L, Tlen) >> 1, 30), u >= bestU ? bestS + 1 : bestS);
@@ -683,6 +757,8 @@ __global__ __launch_bounds__(64, W) void sw_cont_kernel(SwArgs a) {
                         return false;
                     }
                 }
+                // (Skipping the resolve while every pending lane's continuation candidate outscores its trunk best -- exact,
+                //  the note stays valid -- was measured and does not pay: DESIGN section 7.)
                 resolve_best<R>(T, row0, row0g, geK, rowbuf);
                 bk = T.bestkey, bs = T.beststart;
                 const bool c = m > bk;     // an equal key is impossible: trunk cells end at columns <= col
