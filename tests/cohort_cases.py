@@ -1,6 +1,7 @@
 """The items the cohort unit is tested on (tests/test_cohort_gpu.py), kept apart so that tests/test_cohort_model.py can show
-on the CPU, with the model alone, that every one of them has a call to compare (a gap above 1e-5) and the status it is
-meant to have.  An item is (samples, ploidy): samples a list of (a, b, lw) or None, ploidy one or per sample."""
+on the CPU, with the model alone, that every one of them has a call to compare (a gap above 1e-5; where a tie is intended,
+an exact one and more than 1e-5 beyond it) and the status it is meant to have.  An item is (samples, ploidy): samples a
+list of (a, b, lw) or None, ploidy one or per sample."""
 import json
 import os
 
@@ -132,7 +133,118 @@ REFUSED = {
 }
 
 
+def peaked(n, at, seed, base=10):
+    """crafted(n, seed, base) with its lone 0 at position `at`."""
+    a, b, lw = crafted(n, seed, base)
+    lw[lw == 0.0] = -3.0
+    lw[at] = 0.0
+    return a, b, lw
+
+
+def haploid(n, seed, distinct=None):
+    """A ploidy-1 list of n homozygous pairs: over the alleles 0 .. n - 1 in order, or drawn from 0 .. distinct - 1 with
+    repeats; lw drawn in -30 .. -3 with a lone 0."""
+    rng = np.random.RandomState(seed)
+    a = np.arange(n, dtype=np.int32) if distinct is None else rng.randint(0, distinct, n).astype(np.int32)
+    lw = -rng.uniform(3.0, 30.0, n)
+    lw[rng.randint(n)] = 0.0
+    return a, a.copy(), lw
+
+
+def fillers(n, seed):
+    """n pairs over consecutive alleles from 100 up, lw drawn in -40 .. -30: what a list is padded with."""
+    a, b, _ = crafted(n, seed, base=100)
+    return a, b, -np.random.RandomState(seed).uniform(30.0, 40.0, n)
+
+
+def with_pairs(l, at, pairs):
+    """The list l with the pairs (a, b, lw) put in place of those at the positions `at`."""
+    a, b, lw = (x.copy() for x in l)
+    for k, (x, y, v) in zip(at, pairs):
+        a[k], b[k], lw[k] = x, y, v
+    return a, b, lw
+
+
+def join(*lists):
+    return tuple(np.concatenate([l[i] for l in lists]) for i in range(3))
+
+
+# The workgroup path (lists of more than LONG_LIST pairs) at the edges of its strides and wavefronts, and at ploidy 1.
+LONG_PEAKS = [(LONG_LIST + 1, at) for at in (0, 63, 64, 255, 256, 1023, 1024)] + [(2 * LONG_LIST + 1, at) for at in (2047, 2048)]
+CASES["long_list_edges"] = lambda: ([([peaked(n, at, 300 + at) for n, at in LONG_PEAKS], 2),
+                                     ([haploid(CAP + 1, 31), haploid(1500, 32, distinct=200)], 1)], dict(iters=16))
+
+# Exact ties.  Two mechanisms make them exact on any device: a pair that stands twice in a list -- the same q bit for bit
+# under any f, the earlier one wins -- and an item that is invariant under swapping the alleles 5 and 7, whose f(5) and f(7)
+# are equal bit for bit by induction over the iterations (their incidence lists have the same length, order and values): the
+# call is the pair with a = 5, although it comes second.
+# (n, i, j): a list of n pairs with the pair (6, 8, 0) at i and j.  The wavefront's path: the lanes 0 and 1, one lane in two
+# strides, the last partial stride.  The workgroup's: one wavefront, two wavefronts, one thread in two strides, the last
+# partial stride.
+DUPLICATES = [(100, 0, 1), (100, 5, 69), (150, 129, 149), (150, 60, 149),
+              (1100, 10, 20), (1100, 10, 138), (1100, 10, 266), (1100, 200, 1099), (1100, 1030, 1090)]
+SYM, SYM_HOMO = lst((7, 9, 0.0), (5, 9, 0.0), (9, 9, -3.0)), lst((7, 7, 0.0), (5, 5, 0.0), (9, 9, -3.0))
+TIES = {
+    "duplicates": lambda: ([([with_pairs(fillers(n, 400 + k), (i, j), [(6, 8, 0.0)] * 2) for k, (n, i, j) in enumerate(DUPLICATES)], 2)],
+                           dict(iters=16)),
+    "symmetric": lambda: ([([SYM, SYM_HOMO, join(fillers(70, 41), SYM), join(fillers(1100, 42), SYM), SYM], 2)], dict(iters=16)),
+    "symmetric_ploidy_1": lambda: ([([lst((7, 7, 0.0), (5, 5, 0.0), (9, 9, -1.0)), SYM], [1, 2])], dict(iters=16)),
+}
+TIE_CALLS = {"duplicates": [[i for _, i, _ in DUPLICATES]], "symmetric": [[1, 1, 71, 1101, 1]], "symmetric_ploidy_1": [[1, 1]]}
+
+
+def _long_refused(changes, ploidy=2):
+    """_GOOD and a list of 1100 pairs, changed at {index: (a, b, lw)}."""
+    l = haploid(1100, 51, distinct=300) if ploidy == 1 else peaked(1100, 17, 52)
+    at = sorted(changes)
+    return _GOOD + [with_pairs(l, at, [changes[k] for k in at])], [2, 2, ploidy]
+
+
+REFUSED.update({
+    "long_a_above_b_in_wavefront_3": lambda: (_long_refused({200: (30, 20, -5.0)}), cm.BAD_ITEM),
+    "long_a_above_b_in_the_second_stride": lambda: (_long_refused({1024: (30, 20, -5.0)}), cm.BAD_ITEM),
+    "long_nan_last": lambda: (_long_refused({1099: (20, 30, float("nan"))}), cm.BAD_ITEM),
+    "long_allele_1025": lambda: (_long_refused({300: (20, CAP + 1, -5.0)}), cm.TOO_LONG),
+    "long_bad_before_too_long": lambda: (_long_refused({100: (20, CAP + 1, -5.0), 900: (30, 20, -5.0)}), cm.BAD_ITEM),
+    "long_heterozygous_at_ploidy_1": lambda: (_long_refused({700: (3, 4, -5.0)}, ploidy=1), cm.BAD_ITEM),
+})
+
+# The classes of the call beyond the launch caps (tests/test_cohort_gpu.py): supports of 3, 4, 4 and 6 alleles, a refused
+# and an empty item.
+BIG_CLASSES = [small_item(2), ([crafted(10, 11)], 2),
+               ([lst((3, 3, -1.0), (3, 8, 0.0), (8, 20, -2.5)), one(20, 20), lst((2, 2, 0.0), (8, 8, -1.0))], [2, 2, 1]),
+               REFUSED["a_above_b"]()[0], REFUSED["empty"]()[0], ([crafted(21, 12, base=0), one(3, 3)], 2)]
+BIG_N, BIG_ITERS = 70000, 3
+OTHER_ALLELES = ([lst((1, 1, -0.5), (1, 4, 0.0), (4, 700, -1.0)), one(4, 4)], 2)    # a small item over alleles of its own
+
+
+def big_call():
+    """The class of every item of the big call: more than 65 536 items and more than 4 x 65 536 chunks."""
+    return np.random.RandomState(70).choice(len(BIG_CLASSES), BIG_N, p=[0.1, 0.3, 0.15, 0.05, 0.05, 0.35])
+
+
 def batch_of_nine(golden):
     """Nine items, a refused and an empty one in the middle."""
     return [small_item(4), CASES["mixed_ploidy"]()[0][0], golden, REFUSED["a_above_b"]()[0], REFUSED["empty"]()[0],
             support_item(65), _sizes(), CASES["lw_minus_800"]()[0][0], entries_item(70)]
+
+
+GOLDEN_PARAMS = [dict(iters=1), dict(iters=2), dict(iters=64), dict(iters=64, alpha=1e-6), dict(iters=64, alpha=100.0)]
+
+
+def compared(golden):
+    """(name, item, parameters, ties) of every item the GPU tests compare with the model."""
+    for params in GOLDEN_PARAMS:
+        yield "golden", golden, params, False
+    for group, ties in ((CASES, False), (TIES, True)):
+        for name, make in group.items():
+            items, params = make()
+            for item in items:
+                yield name, item, params, ties
+    for item in batch_of_nine(golden):
+        yield "batch_of_nine", item, dict(iters=7), False
+    for item in BIG_CLASSES:
+        yield "big_call", item, dict(iters=BIG_ITERS), False
+    yield "small_item(3)", small_item(3), dict(iters=5), False
+    yield "other_alleles", OTHER_ALLELES, dict(iters=5), False
+    yield "iteration_cap", small_item(2), dict(iters=cm.MAX_ITERS), False

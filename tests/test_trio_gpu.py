@@ -274,6 +274,27 @@ def test_a_batch_of_nine_equals_its_items_one_by_one(ctx, golden):
         assert x[:3] == y[:3] and x[3].tobytes() == y[3].tobytes()
 
 
+def test_a_call_beyond_the_launch_caps(ctx):
+    """70 000 items of six classes: more items than a launch has workgroups (65 536), so trio_prepare_kernel and
+    trio_child_kernel stride over the items, and twice as many gamete work units and more, so trio_gamete_kernel strides and
+    finds an item by its binary search over tile counts that differ from class to class.  Every item has the bits of its
+    class alone, and every class is the model's."""
+    rng = np.random.default_rng(70)
+    ok, bad = _bad_lists()
+    empty = (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0))
+    classes = [Item(crafted(rng, 5), crafted(rng, 7), crafted(rng, 9)), Item(crafted(rng, 40), crafted(rng, 12), crafted(rng, 3)),
+               Item(crafted(rng, 6), None, crafted(rng, 8)), Item(bad["a above b"], ok, ok), Item(empty, ok, ok),
+               Item(crafted(rng, 70, distinct=40), crafted(rng, 20), crafted(rng, 20))]
+    alone = check(ctx, classes)
+    assert [a[0] for a in alone] == [tm.OK, tm.OK, tm.OK, tm.BAD_ITEM, tm.EMPTY_CHILD, tm.OK]
+    which = rng.choice(len(classes), 70000, p=[0.3, 0.2, 0.15, 0.05, 0.05, 0.25])
+    tiles = [(min(2 * len(c.child[0]), CAP + 1) + TILE - 1) // TILE for c in classes]
+    assert tiles == [1, 2, 1, 1, 0, 3] and len(which) > 65536 and 2 * sum(tiles[c] for c in which) > 2 * 65536
+    got, _ = run(ctx, [classes[c] for c in which])
+    wrong = [i for i, (g, c) in enumerate(zip(got, which)) if g[:3] != alone[c][:3] or g[3].tobytes() != alone[c][3].tobytes()]
+    assert not wrong, (len(wrong), wrong[:10], [int(which[i]) for i in wrong[:10]])
+
+
 @pytest.mark.parametrize("params", [dict(mu=1e-6), dict(mu=0.5), dict(rho=0.01), dict(rho=0.99), dict(beta=0.0), dict(beta=1.0),
                                     dict(mu=0.3, rho=0.7, beta=0.2)])
 def test_parameters(ctx, golden, params):
