@@ -35,7 +35,6 @@ struct tredgpu_ctx {
     // ladders
     std::vector<LadderDesc> h_ladders;
     Buf d_ladders, d_seq;
-    int max_templates = 0;  // max over ladders of 2*max_units (or 1)
     int max_ladder_units = 0;
     // model
     Buf d_model;
@@ -45,7 +44,7 @@ struct tredgpu_ctx {
     int* h_pin = nullptr;  // pinned word for small read-backs
     hipEvent_t sync_ev = nullptr;  // stream_sync's event
     size_t grid_pool_bytes = GRID_POOL_BYTES;   // TREDGPU_GRID_POOL_MB overrides (tuning / tests of the multi-pass path)
-    Buf st[40];  // staging for HOST-memory calls
+    std::vector<Buf> st;  // the arrays of a HOST-memory call, in the order of the call's list (stage)
     // pinned arena of the HOST-memory calls: copies from / to the caller's pageable arrays go through it, so that they are
     // truly asynchronous (a hipMemcpyAsync on pageable memory is staged and waited for by the runtime, one by one -- with
     // several driver processes on the device each of those waits queues behind the others' work: 25 per batch)
@@ -53,8 +52,6 @@ struct tredgpu_ctx {
     std::vector<PinBlock> pin;
     struct PinOut { void* host; const void* pinned; size_t bytes; };
     std::vector<PinOut> pin_out;       // read-backs to hand over at the next stream_sync
-    // intermediates of the fused path
-    Buf ws_tag, ws_h, ws_score;
     // HIP-event timing of the three main kernels
     struct Timer {
         std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;  // reusable event pairs
@@ -76,10 +73,15 @@ int fail(tredgpu_ctx* c, int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIPCHK(c, expr)                                                                    \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) return fail((c), -10, "%s: %s", #expr, hipGetErrorString(e_)); \
+int hip_rc(tredgpu_ctx* c, hipError_t e, const char* what) {
+    return e == hipSuccess ? 0 : fail(c, -10, "%s: %s", what, hipGetErrorString(e));
+}
+
+// 0, or -10 with the call's text and HIP's; HIPCHK returns it from the function
+#define HIPRC(c, expr) hip_rc((c), (expr), #expr)
+#define HIPCHK(c, expr)                          \
+    do {                                         \
+        if (int rc_ = HIPRC(c, expr)) return rc_; \
     } while (0)
 
 // resolve the recorded event pairs of one timer into (launches, total_ms); stream must be idle
@@ -133,9 +135,9 @@ void* pin_alloc(tredgpu_ctx* c, size_t bytes) {
     return p;
 }
 
-// wait for the context's stream; then hand the read-backs that went through the pinned arena to their arrays and start
-// the arena afresh (nothing of it is in flight any more)
-hipError_t stream_sync(tredgpu_ctx* c) {
+// wait for the context's stream; then hand the read-backs that went through the pinned arena to their arrays (deliver
+// false: drop them, the way out of a failed call) and start the arena afresh (nothing of it is in flight any more)
+hipError_t stream_sync(tredgpu_ctx* c, bool deliver = true) {
     // hipStreamSynchronize spins: a driver process whose genotyping call shares the device with three processes' decoders
     // sits in it for 40 ms per call -- a core per driver burnt on a box that is short of cores (8 CPUs: 36 k genotypes/s).
     // So: a short spin for the calls that are nearly done (the kernel-path benchmark's step ends within microseconds of
@@ -154,7 +156,7 @@ hipError_t stream_sync(tredgpu_ctx* c) {
         }
     } else
         e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess)
+    if (e == hipSuccess && deliver)
         for (const auto& o : c->pin_out) memcpy(o.host, o.pinned, o.bytes);
     c->pin_out.clear();
     for (auto& b : c->pin) b.used = 0;
@@ -243,38 +245,104 @@ int check_sw_range(tredgpu_ctx* c, const tredgpu_sw_params* p, int max_len) {
     return 0;
 }
 
-// copy a host array to a staging buffer; returns device pointer through out
-template <typename T>
-int stage_in(tredgpu_ctx* c, Buf& b, const T* host, size_t n, const T** out) {
-    int rc = ensure(c, b, n * sizeof(T));
-    if (rc) return rc;
-    if (n) {
-        void* h = pin_alloc(c, n * sizeof(T));
-        if (!h) return fail(c, -10, "no pinned memory for a %zu-byte copy", n * sizeof(T));
-        memcpy(h, host, n * sizeof(T));
-        HIPCHK(c, hipMemcpyAsync(b.p, h, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+// One array of a HOST-memory call, as the call's list names it once: the pointer of the call's argument set that stage()
+// points at the device's copy, the caller's array, the bytes of room on the device and the bytes copied.  arr_in: copied
+// to the device by stage(); arr_out: copied back by finish() (copied: fewer elements than the room holds); arr_scratch:
+// on the device only.  An optional array the caller left out is `absent` in the list: its pointer stays null.
+struct Staged {
+    void* slot;
+    const void* src;
+    void* dst;
+    size_t room, bytes;
+};
+const Staged absent = {nullptr, nullptr, nullptr, 0, 0};
+template <class T>
+Staged arr_in(const T*& dev, const T* host, size_t count) { return Staged{&dev, host, nullptr, count * sizeof(T), count * sizeof(T)}; }
+template <class T>
+Staged arr_out(T*& dev, T* host, size_t count) { return Staged{&dev, nullptr, host, count * sizeof(T), count * sizeof(T)}; }
+template <class T>
+Staged arr_out(T*& dev, T* host, size_t count, size_t copied) { return Staged{&dev, nullptr, host, count * sizeof(T), copied * sizeof(T)}; }
+template <class T>
+Staged arr_scratch(T*& dev, size_t count) { return Staged{&dev, nullptr, nullptr, count * sizeof(T), 0}; }
+
+// `bytes` of the pinned arena for one copy of a staged call
+int pin_for(tredgpu_ctx* c, size_t bytes, void** h) {
+    *h = pin_alloc(c, bytes);
+    return *h ? 0 : fail(c, -10, "no pinned memory for a %zu-byte copy", bytes);
+}
+
+// The start of a HOST-memory call: sizes the context's buffers for the list -- all of them first: ensure waits for the
+// stream when it regrows one, which starts the arena afresh --, enqueues the copies of its inputs through the arena and
+// points the call's arguments at the device's arrays.  What follows it leaves through finish().
+int stage(tredgpu_ctx* c, const std::vector<Staged>& list) {
+    int rc;
+    if (c->st.size() < list.size()) c->st.resize(list.size());
+    for (size_t k = 0; k < list.size(); ++k)
+        if (list[k].slot && (rc = ensure(c, c->st[k], list[k].room))) return rc;
+    for (size_t k = 0; k < list.size(); ++k) {
+        const Staged& a = list[k];
+        if (!a.slot) continue;
+        if (a.src && a.bytes) {
+            void* h;
+            if ((rc = pin_for(c, a.bytes, &h))) return rc;
+            memcpy(h, a.src, a.bytes);
+            HIPCHK(c, hipMemcpyAsync(c->st[k].p, h, a.bytes, hipMemcpyHostToDevice, c->stream));
+        }
+        memcpy(a.slot, &c->st[k].p, sizeof(void*));
     }
-    *out = (const T*)b.p;
     return 0;
 }
 
-template <typename T>
-int stage_out(tredgpu_ctx* c, Buf& b, size_t n, T** out) {
-    int rc = ensure(c, b, n * sizeof(T));
-    if (rc) return rc;
-    *out = (T*)b.p;
+// The one way out of a HOST-memory call after stage(), rc: what the call came to.  0: the list's outputs to the caller's
+// arrays through the arena and the call's one wait.  A failure, here or before: the stream is drained all the same --
+// nothing enqueued reads the caller's or an inflater's memory after the call has returned --, the pending read-backs
+// are dropped and rc stays what it was.
+int finish(tredgpu_ctx* c, const std::vector<Staged>& list, int rc) {
+    for (size_t k = 0; k < list.size() && !rc; ++k) {
+        const Staged& a = list[k];
+        if (!a.dst || !a.bytes) continue;
+        void* h;
+        if ((rc = pin_for(c, a.bytes, &h))) break;
+        rc = HIPRC(c, hipMemcpyAsync(h, c->st[k].p, a.bytes, hipMemcpyDeviceToHost, c->stream));
+        if (!rc) c->pin_out.push_back({a.dst, h, a.bytes});       // handed over by stream_sync
+    }
+    if (rc) {
+        (void)stream_sync(c, false);
+        return rc;
+    }
+    return HIPRC(c, stream_sync(c));
+}
+
+// The checks of unit g of a HOST-memory call, in the order the fused calls make them: its ladder registered, hist_stride
+// against that ladder's max_units (the histograms must hold the repeat counts of THIS batch's ladders; the context may
+// know longer ones), the paired-end slices, marg_stride.  unit_ladder NULL: a call without ladders (the grid's);
+// marg_stride 0: no marginals asked for.  limits: {max maxinsert, max n_target} so far.
+int check_unit(tredgpu_ctx* c, int g, const tredgpu_unit_params& u, const int32_t* unit_ladder, int32_t hist_stride,
+               int64_t n_global_total, int64_t n_target_total, int32_t marg_stride, int limits[2]) {
+    if (unit_ladder) {
+        const int lad = unit_ladder[g];
+        if (lad < 0 || lad >= (int)c->h_ladders.size()) return fail(c, -2, "unit %d: ladder %d not registered", g, lad);
+        if (hist_stride <= c->h_ladders[lad].max_units)
+            return fail(c, -2, "hist_stride %d must exceed the max_units %d of unit %d's ladder", hist_stride, c->h_ladders[lad].max_units, g);
+    }
+    limits[0] = std::max(limits[0], u.maxinsert);
+    limits[1] = std::max(limits[1], u.n_target);
+    if (u.n_global < 0 || u.n_target < 0 || u.pe_off < 0 || u.tl_off < 0 || (int64_t)u.pe_off + u.n_global > n_global_total ||
+        (int64_t)u.tl_off + u.n_target > n_target_total)
+        return fail(c, -2, "unit %d: paired-end slices out of range", g);
+    if (marg_stride > 0 && marg_stride <= std::max(u.maxinsert, hist_stride)) return fail(c, -2, "marg_stride must exceed max(maxinsert, hist_stride)");
     return 0;
 }
 
-template <typename T>
-int copy_back(tredgpu_ctx* c, T* host, const T* dev, size_t n) {
-    if (n && host) {
-        void* h = pin_alloc(c, n * sizeof(T));
-        if (!h) return fail(c, -10, "no pinned memory for a %zu-byte copy", n * sizeof(T));
-        HIPCHK(c, hipMemcpyAsync(h, dev, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
-        c->pin_out.push_back({host, h, n * sizeof(T)});       // handed over by stream_sync
-    }
-    return 0;
+// The read-length bound of a HOST-memory call (the lengths are looked at): params.max_read_len where the caller names
+// one, else the longest read, which may select a larger instantiation than the one the arguments alone were checked for
+// -- so the scoring is checked again, for that one.  A read beyond TREDGPU_MAX_READ_LEN is refused, never truncated.
+int host_max_len(tredgpu_ctx* c, const tredgpu_sw_params* p, const int32_t* read_len, int64_t n_reads, int* max_len) {
+    int seen = 0;
+    for (int64_t r = 0; r < n_reads; ++r) seen = std::max(seen, read_len[r]);
+    if (seen > TREDGPU_MAX_READ_LEN) return fail(c, -5, "read of %d bp exceeds TREDGPU_MAX_READ_LEN=%d", seen, TREDGPU_MAX_READ_LEN);
+    *max_len = std::max(p->max_read_len > 0 ? p->max_read_len : seen, 1);
+    return check_sw_range(c, p, *max_len);
 }
 
 }  // namespace
@@ -323,7 +391,7 @@ void tredgpu_destroy(tredgpu_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)stream_sync(c);
     for (Buf* b : {&c->d_ladders, &c->d_seq, &c->d_model, &c->ws_quads, &c->ws_counter, &c->ws_drop,
-                   &c->ws_grid, &c->ws_stats, &c->ws_perm, &c->ws_class, &c->ws_gdesc, &c->ws_gtile, &c->ws_gctr, &c->ws_ucnt, &c->ws_bins, &c->ws_kde, &c->ws_tag, &c->ws_h, &c->ws_score})
+                   &c->ws_grid, &c->ws_stats, &c->ws_perm, &c->ws_class, &c->ws_gdesc, &c->ws_gtile, &c->ws_gctr, &c->ws_ucnt, &c->ws_bins, &c->ws_kde})
         release(*b);
     for (Buf& b : c->st) release(b);
     for (auto& t : c->timers)
@@ -399,7 +467,7 @@ int tredgpu_set_ladders(tredgpu_ctx* c, int32_t n, const char* const* prefix, co
         return off;
     };
     std::vector<LadderDesc> lad((size_t)n);
-    int max_t = 1, max_u = 0;
+    int max_u = 0;
     for (int i = 0; i < n; ++i) {
         std::vector<int8_t> P, Rp, S;
         encode(prefix[i], P);
@@ -466,7 +534,6 @@ int tredgpu_set_ladders(tredgpu_ctx* c, int32_t n, const char* const* prefix, co
             d.kmer_off[s] = (int)seq.size();
             seq.insert(seq.end(), bits.begin(), bits.end());
         }
-        max_t = std::max(max_t, 2 * mu);
         max_u = std::max(max_u, mu);
     }
     seq.resize(seq.size() + 4, 0x44444444u);
@@ -477,7 +544,6 @@ int tredgpu_set_ladders(tredgpu_ctx* c, int32_t n, const char* const* prefix, co
     if (n) HIPCHK(c, hipMemcpy(c->d_ladders.p, lad.data(), lad.size() * sizeof(LadderDesc), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_seq.p, seq.data(), seq.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     c->h_ladders.swap(lad);
-    c->max_templates = max_t;
     c->max_ladder_units = max_u;
     return 0;
 }
@@ -616,36 +682,21 @@ int tredgpu_sw_classify(tredgpu_ctx* c, int mem, const uint32_t* packed, const i
         if (unit_read_off[g + 1] < unit_read_off[g]) return fail(c, -2, "unit_read_off not monotone at %d", g);
         if (unit_ladder[g] < 0 || unit_ladder[g] >= (int)c->h_ladders.size()) return fail(c, -2, "unit %d: ladder %d not registered", g, unit_ladder[g]);
     }
-    int seen = 0;
-    for (int64_t r = 0; r < n_reads; ++r) seen = std::max(seen, read_len[r]);
-    if (max_len <= 0) max_len = seen;
-    if (seen > TREDGPU_MAX_READ_LEN) return fail(c, -5, "read of %d bp exceeds TREDGPU_MAX_READ_LEN=%d", seen, TREDGPU_MAX_READ_LEN);
-    if ((rc = check_sw_range(c, params, std::max(max_len, 1)))) return rc;     // the instantiation these reads select
+    if ((rc = host_max_len(c, params, read_len, n_reads, &max_len))) return rc;
     const uint32_t* d_packed; const int64_t* d_off; const int32_t* d_len; const int32_t* d_uoff; const int32_t* d_ulad;
     uint8_t* d_tag; int16_t* d_h; int16_t* d_score; int16_t* d_dump = nullptr;
-    const size_t words = (size_t)read_off[n_reads];
-    if ((rc = stage_in(c, c->st[0], packed, words, &d_packed))) return rc;
-    if ((rc = stage_in(c, c->st[1], read_off, (size_t)n_reads + 1, &d_off))) return rc;
-    if ((rc = stage_in(c, c->st[2], read_len, (size_t)n_reads, &d_len))) return rc;
-    if ((rc = stage_in(c, c->st[3], unit_read_off, (size_t)n_units + 1, &d_uoff))) return rc;
-    if ((rc = stage_in(c, c->st[4], unit_ladder, (size_t)n_units, &d_ulad))) return rc;
-    if ((rc = stage_out(c, c->st[5], (size_t)n_reads, &d_tag))) return rc;
-    if ((rc = stage_out(c, c->st[6], (size_t)n_reads, &d_h))) return rc;
-    if ((rc = stage_out(c, c->st[7], (size_t)n_reads, &d_score))) return rc;
-    const size_t dump_n = out_dump ? (size_t)n_reads * dump_templates * 6 : 0;
-    if (out_dump) {
-        if ((rc = stage_out(c, c->st[8], dump_n, &d_dump))) return rc;
-        HIPCHK(c, hipMemsetAsync(d_dump, 0xFF, dump_n * sizeof(int16_t), c->stream));
-    }
-    if ((rc = run_sw_device(c, d_packed, d_off, d_len, n_reads, d_uoff, d_ulad, n_units, params, max_len, d_tag,
-                            d_h, d_score, d_dump, dump_templates)))
-        return rc;
-    if ((rc = copy_back(c, out_tag, (const uint8_t*)d_tag, (size_t)n_reads))) return rc;
-    if ((rc = copy_back(c, out_h, (const int16_t*)d_h, (size_t)n_reads))) return rc;
-    if ((rc = copy_back(c, out_score, (const int16_t*)d_score, (size_t)n_reads))) return rc;
-    if ((rc = copy_back(c, out_dump, (const int16_t*)d_dump, dump_n))) return rc;
-    HIPCHK(c, stream_sync(c));
-    return 0;
+    const size_t n = (size_t)n_reads, g = (size_t)n_units, dump_n = out_dump ? n * dump_templates * 6 : 0;
+    const std::vector<Staged> list = {
+        arr_in(d_packed, packed, (size_t)read_off[n_reads]), arr_in(d_off, read_off, n + 1), arr_in(d_len, read_len, n),
+        arr_in(d_uoff, unit_read_off, g + 1), arr_in(d_ulad, unit_ladder, g),
+        arr_out(d_tag, out_tag, n), arr_out(d_h, out_h, n), arr_out(d_score, out_score, n),
+        out_dump ? arr_out(d_dump, out_dump, dump_n) : absent,
+    };
+    rc = stage(c, list);
+    if (!rc && out_dump) rc = HIPRC(c, hipMemsetAsync(d_dump, 0xFF, dump_n * sizeof(int16_t), c->stream));
+    if (!rc) rc = run_sw_device(c, d_packed, d_off, d_len, n_reads, d_uoff, d_ulad, n_units, params, max_len, d_tag, d_h,
+                                d_score, d_dump, dump_templates);
+    return finish(c, list, rc);
 }
 
 int tredgpu_tally(tredgpu_ctx* c, int mem, const uint8_t* tag, const int16_t* h, int64_t n_reads,
@@ -667,24 +718,18 @@ int tredgpu_tally(tredgpu_ctx* c, int mem, const uint8_t* tag, const int16_t* h,
     if (mem != TREDGPU_MEM_HOST) return fail(c, -2, "bad mem");
     const uint8_t* d_tag; const int16_t* d_h; const int32_t* d_uoff; const int32_t* d_pid = nullptr;
     int32_t *d_f, *d_p, *d_r;
-    const size_t hn = (size_t)n_units * hist_stride;
-    if ((rc = stage_in(c, c->st[0], tag, (size_t)n_reads, &d_tag))) return rc;
-    if ((rc = stage_in(c, c->st[1], h, (size_t)n_reads, &d_h))) return rc;
-    if ((rc = stage_in(c, c->st[2], unit_read_off, (size_t)n_units + 1, &d_uoff))) return rc;
-    if (read_pair_id && (rc = stage_in(c, c->st[3], read_pair_id, (size_t)n_reads, &d_pid))) return rc;
-    if ((rc = stage_out(c, c->st[4], hn, &d_f))) return rc;
-    if ((rc = stage_out(c, c->st[5], hn, &d_p))) return rc;
-    if ((rc = stage_out(c, c->st[6], hn, &d_r))) return rc;
-    {
+    const size_t n = (size_t)n_reads, hn = (size_t)n_units * hist_stride;
+    const std::vector<Staged> list = {
+        arr_in(d_tag, tag, n), arr_in(d_h, h, n), arr_in(d_uoff, unit_read_off, (size_t)n_units + 1),
+        read_pair_id ? arr_in(d_pid, read_pair_id, n) : absent,
+        arr_out(d_f, full_cnt, hn), arr_out(d_p, pref_cnt, hn), arr_out(d_r, rept_cnt, hn),
+    };
+    if (!(rc = stage(c, list))) {
         ScopedTimer tm(c, TREDGPU_KERNEL_TALLY);
-        HIPCHK(c, launch_tally(d_tag, d_h, n_reads, d_uoff, n_units, d_pid, hist_stride, d_f, d_p, d_r,
-                               (uint8_t*)c->ws_drop.p, c->stream));
+        rc = HIPRC(c, launch_tally(d_tag, d_h, n_reads, d_uoff, n_units, d_pid, hist_stride, d_f, d_p, d_r,
+                                   (uint8_t*)c->ws_drop.p, c->stream));
     }
-    if ((rc = copy_back(c, full_cnt, (const int32_t*)d_f, hn))) return rc;
-    if ((rc = copy_back(c, pref_cnt, (const int32_t*)d_p, hn))) return rc;
-    if ((rc = copy_back(c, rept_cnt, (const int32_t*)d_r, hn))) return rc;
-    HIPCHK(c, stream_sync(c));
-    return 0;
+    return finish(c, list, rc);
 }
 
 // ---- likelihood grid -------------------------------------------------------------------------------
@@ -812,55 +857,25 @@ static int likelihood_grid_impl(tredgpu_ctx* c, int mem, const tredgpu_unit_para
     if (mem != TREDGPU_MEM_HOST) return fail(c, -2, "bad mem");
     if (n_units == 0) return 0;
     int limits[2] = {0, 0};
-    for (int g = 0; g < n_units; ++g) {
-        limits[0] = std::max(limits[0], units[g].maxinsert);
-        limits[1] = std::max(limits[1], units[g].n_target);
-    }
-    for (int g = 0; g < n_units; ++g) {
-        const tredgpu_unit_params& u = units[g];
-        if (u.n_global < 0 || u.n_target < 0 || u.pe_off < 0 || u.tl_off < 0 || (int64_t)u.pe_off + u.n_global > n_global_total ||
-            (int64_t)u.tl_off + u.n_target > n_target_total)
-            return fail(c, -2, "unit %d: paired-end slices out of range", g);
-        if (marg && marg_stride <= std::max(u.maxinsert, hist_stride)) return fail(c, -2, "marg_stride must exceed max(maxinsert, hist_stride)");
-    }
-    const tredgpu_unit_params* d_units; const int32_t *d_f, *d_p, *d_r, *d_gl = nullptr, *d_tl = nullptr;
+    for (int g = 0; g < n_units; ++g)
+        if ((rc = check_unit(c, g, units[g], nullptr, hist_stride, n_global_total, n_target_total, marg ? marg_stride : 0, limits))) return rc;
+    const tredgpu_unit_params* d_units; const int32_t *d_f, *d_p, *d_r, *d_gl, *d_tl;
     const int64_t* d_goff = nullptr; tredgpu_call* d_calls; double* d_dump = nullptr; double* d_marg = nullptr;
-    const size_t hn = (size_t)n_units * hist_stride;
-    if ((rc = stage_in(c, c->st[0], units, (size_t)n_units, &d_units))) return rc;
-    if ((rc = stage_in(c, c->st[1], full_cnt, hn, &d_f))) return rc;
-    if ((rc = stage_in(c, c->st[2], pref_cnt, hn, &d_p))) return rc;
-    if ((rc = stage_in(c, c->st[3], rept_cnt, hn, &d_r))) return rc;
-    if ((rc = stage_in(c, c->st[4], global_lens, (size_t)n_global_total, &d_gl))) return rc;
-    if ((rc = stage_in(c, c->st[5], target_lens, (size_t)n_target_total, &d_tl))) return rc;
-    if ((rc = stage_out(c, c->st[6], (size_t)n_units, &d_calls))) return rc;
-    size_t dump_n = 0;
-    if (grid_off) {
-        dump_n = (size_t)grid_off[n_units] * 6;
-        if ((rc = stage_in(c, c->st[7], grid_off, (size_t)n_units + 1, &d_goff))) return rc;
-        if ((rc = stage_out(c, c->st[8], dump_n, &d_dump))) return rc;
-    }
-    const size_t marg_n = marg ? (size_t)n_units * 2 * marg_stride : 0;
-    if (marg && (rc = stage_out(c, c->st[9], marg_n, &d_marg))) return rc;
     const int64_t* d_joff = nullptr; double* d_joint = nullptr; int32_t* d_jn = nullptr; double* d_jt = nullptr;
-    size_t joint_len = 0;
-    if (joint_off) {
-        joint_len = (size_t)joint_off[n_units] * 3;
-        if ((rc = stage_in(c, c->st[10], joint_off, (size_t)n_units + 1, &d_joff))) return rc;
-        if ((rc = stage_out(c, c->st[11], joint_len, &d_joint))) return rc;
-        if ((rc = stage_out(c, c->st[12], (size_t)n_units, &d_jn))) return rc;
-        if ((rc = stage_out(c, c->st[13], (size_t)n_units, &d_jt))) return rc;
-    }
-    if ((rc = run_grid_device(c, d_units, n_units, hist_stride, d_f, d_p, d_r, d_gl, d_tl, d_calls, d_goff, d_dump,
-                              d_marg, marg_stride, limits, d_joff, d_joint, d_jn, d_jt)))
-        return rc;
-    if ((rc = copy_back(c, joint, (const double*)d_joint, joint_len))) return rc;
-    if ((rc = copy_back(c, joint_n, (const int32_t*)d_jn, joint_off ? (size_t)n_units : 0))) return rc;
-    if ((rc = copy_back(c, joint_total, (const double*)d_jt, joint_off ? (size_t)n_units : 0))) return rc;
-    if ((rc = copy_back(c, calls, (const tredgpu_call*)d_calls, (size_t)n_units))) return rc;
-    if ((rc = copy_back(c, grid_dump, (const double*)d_dump, dump_n))) return rc;
-    if ((rc = copy_back(c, marg, (const double*)d_marg, marg_n))) return rc;
-    HIPCHK(c, stream_sync(c));
-    return 0;
+    const size_t g = (size_t)n_units, hn = g * hist_stride;
+    const std::vector<Staged> list = {
+        arr_in(d_units, units, g), arr_in(d_f, full_cnt, hn), arr_in(d_p, pref_cnt, hn), arr_in(d_r, rept_cnt, hn),
+        arr_in(d_gl, global_lens, (size_t)n_global_total), arr_in(d_tl, target_lens, (size_t)n_target_total),   // (always: 16 bytes when empty)
+        arr_out(d_calls, calls, g),
+        grid_off ? arr_in(d_goff, grid_off, g + 1) : absent, grid_off ? arr_out(d_dump, grid_dump, (size_t)grid_off[n_units] * 6) : absent,
+        marg ? arr_out(d_marg, marg, g * 2 * marg_stride) : absent,
+        joint_off ? arr_in(d_joff, joint_off, g + 1) : absent, joint_off ? arr_out(d_joint, joint, (size_t)joint_off[n_units] * 3) : absent,
+        joint_off ? arr_out(d_jn, joint_n, g) : absent, joint_off ? arr_out(d_jt, joint_total, g) : absent,
+    };
+    rc = stage(c, list);
+    if (!rc) rc = run_grid_device(c, d_units, n_units, hist_stride, d_f, d_p, d_r, d_gl, d_tl, d_calls, d_goff, d_dump, d_marg,
+                                  marg_stride, limits, d_joff, d_joint, d_jn, d_jt);
+    return finish(c, list, rc);
 }
 
 int tredgpu_likelihood_grid(tredgpu_ctx* c, int mem, const tredgpu_unit_params* units, int32_t n_units,
@@ -905,19 +920,42 @@ int tredgpu_pe_kde(tredgpu_ctx* c, int mem, const tredgpu_unit_params* units, in
     }
     if (mem != TREDGPU_MEM_HOST) return fail(c, -2, "bad mem");
     const tredgpu_unit_params* d_units; const int32_t* d_gl; double* d_pdf; int32_t* d_st;
-    if ((rc = stage_in(c, c->st[0], units, (size_t)n_units, &d_units))) return rc;
-    if ((rc = stage_in(c, c->st[1], global_lens, (size_t)n_global_total, &d_gl))) return rc;
-    if ((rc = stage_out(c, c->st[2], (size_t)n_units * TREDGPU_SPAN, &d_pdf))) return rc;
-    if ((rc = stage_out(c, c->st[3], (size_t)n_units, &d_st))) return rc;
-    a.units = d_units;
-    a.global_lens = d_gl;
-    a.kde_pdf = d_pdf;
-    a.kde_status = d_st;
-    HIPCHK(c, launch_pe_kde(a, c->stream));
-    if ((rc = copy_back(c, pdf_out, (const double*)d_pdf, (size_t)n_units * TREDGPU_SPAN))) return rc;
-    if ((rc = copy_back(c, status_out, (const int32_t*)d_st, (size_t)n_units))) return rc;
-    HIPCHK(c, stream_sync(c));
-    return 0;
+    const std::vector<Staged> list = {
+        arr_in(d_units, units, (size_t)n_units), arr_in(d_gl, global_lens, (size_t)n_global_total),
+        arr_out(d_pdf, pdf_out, (size_t)n_units * TREDGPU_SPAN), arr_out(d_st, status_out, (size_t)n_units),
+    };
+    if (!(rc = stage(c, list))) {
+        a.units = d_units;
+        a.global_lens = d_gl;
+        a.kde_pdf = d_pdf;
+        a.kde_status = d_st;
+        rc = HIPRC(c, launch_pe_kde(a, c->stream));
+    }
+    return finish(c, list, rc);
+}
+
+// SW + tagging -> histograms -> grid on arrays in DEVICE memory, nothing waited for in between: what the fused calls stage
+// for and what the DEVICE branch of tredgpu_genotype_batch runs on the caller's arrays.  read_pair_id: ws_drop is the
+// caller's to size.
+static int run_fused_device(tredgpu_ctx* c, const uint32_t* packed, const int64_t* read_off, const int32_t* read_len, int64_t n_reads,
+                            const int32_t* unit_read_off, const int32_t* unit_ladder, const tredgpu_unit_params* units,
+                            int32_t n_units, const tredgpu_sw_params* params, int max_len, const int32_t* read_pair_id,
+                            const int32_t* global_lens, const int32_t* target_lens, uint8_t* out_tag, int16_t* out_h,
+                            int16_t* out_score, int32_t hist_stride, int32_t* full_cnt, int32_t* pref_cnt, int32_t* rept_cnt,
+                            tredgpu_call* calls, double* marg, int32_t marg_stride, const int* limits,
+                            const int64_t* joint_off = nullptr, double* joint = nullptr, int32_t* joint_n = nullptr,
+                            double* joint_total = nullptr) {
+    int rc;
+    if (n_reads > 0 && (rc = run_sw_device(c, packed, read_off, read_len, n_reads, unit_read_off, unit_ladder, n_units, params,
+                                           max_len, out_tag, out_h, out_score, nullptr, 0)))
+        return rc;
+    {
+        ScopedTimer tm(c, TREDGPU_KERNEL_TALLY);
+        HIPCHK(c, launch_tally(out_tag, out_h, n_reads, unit_read_off, n_units, read_pair_id, hist_stride, full_cnt, pref_cnt,
+                               rept_cnt, (uint8_t*)c->ws_drop.p, c->stream));
+    }
+    return run_grid_device(c, units, n_units, hist_stride, full_cnt, pref_cnt, rept_cnt, global_lens, target_lens, calls,
+                           nullptr, nullptr, marg, marg_stride, limits, joint_off, joint, joint_n, joint_total);
 }
 
 // The whole path for a batch in HOST memory with everything the product's writers print, in ONE call with ONE wait:
@@ -947,72 +985,31 @@ int tredgpu_genotype_batch_joint(tredgpu_ctx* c, const uint32_t* packed, const i
     int limits[2] = {0, 0};
     for (int g = 0; g < n_units; ++g) {
         if (unit_read_off[g + 1] < unit_read_off[g]) return fail(c, -2, "unit_read_off not monotone at %d", g);
-        if (unit_ladder[g] < 0 || unit_ladder[g] >= (int)c->h_ladders.size()) return fail(c, -2, "unit %d: ladder %d not registered", g, unit_ladder[g]);
-        // (the histograms must hold the repeat counts of THIS batch's ladders; the context may know longer ones)
-        if (hist_stride <= c->h_ladders[unit_ladder[g]].max_units)
-            return fail(c, -2, "hist_stride %d must exceed the max_units %d of unit %d's ladder", hist_stride, c->h_ladders[unit_ladder[g]].max_units, g);
-        const tredgpu_unit_params& u = units[g];
-        limits[0] = std::max(limits[0], u.maxinsert);
-        limits[1] = std::max(limits[1], u.n_target);
-        if (u.n_global < 0 || u.n_target < 0 || u.pe_off < 0 || u.tl_off < 0 || (int64_t)u.pe_off + u.n_global > n_global_total ||
-            (int64_t)u.tl_off + u.n_target > n_target_total)
-            return fail(c, -2, "unit %d: paired-end slices out of range", g);
-        if (marg_stride <= std::max(u.maxinsert, hist_stride)) return fail(c, -2, "marg_stride must exceed max(maxinsert, hist_stride)");
+        if ((rc = check_unit(c, g, units[g], unit_ladder, hist_stride, n_global_total, n_target_total, marg_stride, limits))) return rc;
     }
-    int seen = 0;
-    for (int64_t r = 0; r < n_reads; ++r) seen = std::max(seen, read_len[r]);
-    if (seen > TREDGPU_MAX_READ_LEN) return fail(c, -5, "read of %d bp exceeds TREDGPU_MAX_READ_LEN=%d", seen, TREDGPU_MAX_READ_LEN);
-    const int max_len = params->max_read_len > 0 ? params->max_read_len : std::max(seen, 1);
-    if ((rc = check_sw_range(c, params, max_len))) return rc;                  // the instantiation these reads select
-    const uint32_t* d_packed = nullptr; const int64_t* d_off = nullptr; const int32_t* d_len = nullptr;
-    const int32_t *d_uoff, *d_ulad, *d_pid = nullptr, *d_gl = nullptr, *d_tl = nullptr;
+    int max_len;
+    if ((rc = host_max_len(c, params, read_len, n_reads, &max_len))) return rc;
+    if (read_pair_id && (rc = ensure(c, c->ws_drop, (size_t)n_reads))) return rc;
+    const uint32_t* d_packed; const int64_t* d_off; const int32_t *d_len, *d_uoff, *d_ulad, *d_pid = nullptr, *d_gl, *d_tl;
     const tredgpu_unit_params* d_units; const int64_t* d_joff;
     uint8_t* d_tag; int16_t *d_h, *d_score; int32_t *d_f, *d_p, *d_r; tredgpu_call* d_calls; double *d_marg, *d_joint, *d_jt; int32_t* d_jn;
-    const size_t words = n_reads > 0 ? (size_t)read_off[n_reads] : 0, hn = (size_t)n_units * hist_stride;
-    const size_t marg_n = (size_t)n_units * 2 * marg_stride, joint_len = (size_t)joint_off[n_units] * 3;
-    if ((rc = stage_in(c, c->st[0], packed, words, &d_packed))) return rc;
-    if ((rc = stage_in(c, c->st[1], read_off, n_reads > 0 ? (size_t)n_reads + 1 : 0, &d_off))) return rc;
-    if ((rc = stage_in(c, c->st[2], read_len, (size_t)n_reads, &d_len))) return rc;
-    if ((rc = stage_in(c, c->st[3], unit_read_off, (size_t)n_units + 1, &d_uoff))) return rc;
-    if ((rc = stage_in(c, c->st[4], unit_ladder, (size_t)n_units, &d_ulad))) return rc;
-    if ((rc = stage_out(c, c->st[5], (size_t)n_reads, &d_tag))) return rc;
-    if ((rc = stage_out(c, c->st[6], (size_t)n_reads, &d_h))) return rc;
-    if ((rc = stage_out(c, c->st[7], (size_t)n_reads, &d_score))) return rc;
-    if (read_pair_id && (rc = stage_in(c, c->st[8], read_pair_id, (size_t)n_reads, &d_pid))) return rc;
-    if (read_pair_id && (rc = ensure(c, c->ws_drop, (size_t)n_reads))) return rc;
-    if ((rc = stage_out(c, c->st[14], hn, &d_f))) return rc;
-    if ((rc = stage_out(c, c->st[15], hn, &d_p))) return rc;
-    if ((rc = stage_out(c, c->st[16], hn, &d_r))) return rc;
-    if ((rc = stage_in(c, c->st[17], units, (size_t)n_units, &d_units))) return rc;
-    if ((rc = stage_in(c, c->st[18], global_lens, (size_t)n_global_total, &d_gl))) return rc;
-    if ((rc = stage_in(c, c->st[19], target_lens, (size_t)n_target_total, &d_tl))) return rc;
-    if ((rc = stage_out(c, c->st[20], (size_t)n_units, &d_calls))) return rc;
-    if ((rc = stage_out(c, c->st[21], marg_n, &d_marg))) return rc;
-    if ((rc = stage_in(c, c->st[22], joint_off, (size_t)n_units + 1, &d_joff))) return rc;
-    if ((rc = stage_out(c, c->st[23], joint_len, &d_joint))) return rc;
-    if ((rc = stage_out(c, c->st[24], (size_t)n_units, &d_jn))) return rc;
-    if ((rc = stage_out(c, c->st[25], (size_t)n_units, &d_jt))) return rc;
-    if (n_reads > 0 && (rc = run_sw_device(c, d_packed, d_off, d_len, n_reads, d_uoff, d_ulad, n_units, params, max_len, d_tag, d_h,
-                                           d_score, nullptr, 0)))
-        return rc;
-    {
-        ScopedTimer tm(c, TREDGPU_KERNEL_TALLY);
-        HIPCHK(c, launch_tally(d_tag, d_h, n_reads, d_uoff, n_units, d_pid, hist_stride, d_f, d_p, d_r, (uint8_t*)c->ws_drop.p, c->stream));
-    }
-    if ((rc = run_grid_device(c, d_units, n_units, hist_stride, d_f, d_p, d_r, d_gl, d_tl, d_calls, nullptr, nullptr, d_marg,
-                              marg_stride, limits, d_joff, d_joint, d_jn, d_jt)))
-        return rc;
-    if ((rc = copy_back(c, out_tag, (const uint8_t*)d_tag, (size_t)n_reads))) return rc;
-    if ((rc = copy_back(c, out_h, (const int16_t*)d_h, (size_t)n_reads))) return rc;
-    if ((rc = copy_back(c, out_score, (const int16_t*)d_score, (size_t)n_reads))) return rc;
-    if ((rc = copy_back(c, rept_cnt, (const int32_t*)d_r, rept_cnt ? hn : 0))) return rc;
-    if ((rc = copy_back(c, joint, (const double*)d_joint, joint_len))) return rc;
-    if ((rc = copy_back(c, joint_n, (const int32_t*)d_jn, (size_t)n_units))) return rc;
-    if ((rc = copy_back(c, joint_total, (const double*)d_jt, (size_t)n_units))) return rc;
-    if ((rc = copy_back(c, calls, (const tredgpu_call*)d_calls, (size_t)n_units))) return rc;
-    if ((rc = copy_back(c, marg, (const double*)d_marg, marg_n))) return rc;
-    HIPCHK(c, stream_sync(c));
-    return 0;
+    const size_t n = (size_t)n_reads, g = (size_t)n_units, hn = g * hist_stride;
+    const std::vector<Staged> list = {
+        // (without reads the caller may pass neither packed nor read_off)
+        arr_in(d_packed, packed, n ? (size_t)read_off[n_reads] : 0), arr_in(d_off, read_off, n ? n + 1 : 0), arr_in(d_len, read_len, n),
+        arr_in(d_uoff, unit_read_off, g + 1), arr_in(d_ulad, unit_ladder, g),
+        arr_out(d_tag, out_tag, n), arr_out(d_h, out_h, n), arr_out(d_score, out_score, n),
+        read_pair_id ? arr_in(d_pid, read_pair_id, n) : absent,
+        arr_scratch(d_f, hn), arr_scratch(d_p, hn), arr_out(d_r, rept_cnt, hn),       // (rept_cnt: copied back where the caller passed it)
+        arr_in(d_units, units, g), arr_in(d_gl, global_lens, (size_t)n_global_total), arr_in(d_tl, target_lens, (size_t)n_target_total),
+        arr_out(d_calls, calls, g), arr_out(d_marg, marg, g * 2 * marg_stride),
+        arr_in(d_joff, joint_off, g + 1), arr_out(d_joint, joint, (size_t)joint_off[n_units] * 3), arr_out(d_jn, joint_n, g), arr_out(d_jt, joint_total, g),
+    };
+    rc = stage(c, list);
+    if (!rc) rc = run_fused_device(c, d_packed, d_off, d_len, n_reads, d_uoff, d_ulad, d_units, n_units, params, max_len, d_pid, d_gl,
+                                   d_tl, d_tag, d_h, d_score, hist_stride, d_f, d_p, d_r, d_calls, d_marg, marg_stride, limits,
+                                   d_joff, d_joint, d_jn, d_jt);
+    return finish(c, list, rc);
 }
 
 // tredgpu_genotype_batch_joint over reads that never left the device (include/tredgpu.h section 5): the units are tasks of
@@ -1063,85 +1060,38 @@ int tredgpu_genotype_selected(tredgpu_ctx* c, const tredgpu_selected_units* segs
         }
     }
     if (g != n_units) return fail(c, -2, "the segments hold %d units, the batch %d", g, (int)n_units);
-    for (int u = 0; u < n_units; ++u) {
-        if (unit_ladder[u] < 0 || unit_ladder[u] >= (int)c->h_ladders.size()) return fail(c, -2, "unit %d: ladder %d not registered", u, unit_ladder[u]);
-        if (hist_stride <= c->h_ladders[unit_ladder[u]].max_units)
-            return fail(c, -2, "hist_stride %d must exceed the max_units %d of unit %d's ladder", hist_stride, c->h_ladders[unit_ladder[u]].max_units, u);
-        const tredgpu_unit_params& up = units[u];
-        limits[0] = std::max(limits[0], up.maxinsert);
-        limits[1] = std::max(limits[1], up.n_target);
-        if (up.n_global < 0 || up.n_target < 0 || up.pe_off < 0 || up.tl_off < 0 || (int64_t)up.pe_off + up.n_global > n_global_total ||
-            (int64_t)up.tl_off + up.n_target > n_target_total)
-            return fail(c, -2, "unit %d: paired-end slices out of range", u);
-        if (marg_stride <= std::max(up.maxinsert, hist_stride)) return fail(c, -2, "marg_stride must exceed max(maxinsert, hist_stride)");
-    }
-    const int max_len = params->max_read_len;
-    const size_t words = (size_t)unit_word_off[n_units], s4_bytes = (size_t)unit_seq4_off[n_units], nm_bytes = (size_t)unit_name_off[n_units];
-    const size_t hn = (size_t)n_units * hist_stride, marg_n = (size_t)n_units * 2 * marg_stride, joint_len = (size_t)joint_off[n_units] * 3;
+    for (int u = 0; u < n_units; ++u)
+        if ((rc = check_unit(c, u, units[u], unit_ladder, hist_stride, n_global_total, n_target_total, marg_stride, limits))) return rc;
+    const size_t n = (size_t)n_reads, offs = n ? n + 1 : 0, nu = (size_t)n_units, hn = nu * hist_stride;
     uint32_t* d_packed; int64_t* d_off; int32_t* d_len; uint8_t* d_seq4; int64_t* d_s4off; uint8_t* d_names; int64_t* d_nmoff;
-    const int32_t *d_uoff, *d_ulad, *d_task, *d_gl = nullptr, *d_tl = nullptr;
+    const int32_t *d_uoff, *d_ulad, *d_task, *d_gl, *d_tl;
     const int64_t *d_uw, *d_us, *d_un, *d_joff;
     const tredgpu_unit_params* d_units;
     uint8_t* d_tag; int16_t *d_h, *d_score; int32_t *d_f, *d_p, *d_r; tredgpu_call* d_calls; double *d_marg, *d_joint, *d_jt; int32_t* d_jn;
-    if ((rc = stage_out(c, c->st[0], words, &d_packed))) return rc;
-    if ((rc = stage_out(c, c->st[1], (size_t)n_reads + 1, &d_off))) return rc;
-    if ((rc = stage_out(c, c->st[2], (size_t)n_reads, &d_len))) return rc;
-    if ((rc = stage_in(c, c->st[3], unit_read_off, (size_t)n_units + 1, &d_uoff))) return rc;
-    if ((rc = stage_in(c, c->st[4], unit_ladder, (size_t)n_units, &d_ulad))) return rc;
-    if ((rc = stage_out(c, c->st[5], (size_t)n_reads, &d_tag))) return rc;
-    if ((rc = stage_out(c, c->st[6], (size_t)n_reads, &d_h))) return rc;
-    if ((rc = stage_out(c, c->st[7], (size_t)n_reads, &d_score))) return rc;
-    if ((rc = stage_out(c, c->st[14], hn, &d_f))) return rc;
-    if ((rc = stage_out(c, c->st[15], hn, &d_p))) return rc;
-    if ((rc = stage_out(c, c->st[16], hn, &d_r))) return rc;
-    if ((rc = stage_in(c, c->st[17], units, (size_t)n_units, &d_units))) return rc;
-    if ((rc = stage_in(c, c->st[18], global_lens, (size_t)n_global_total, &d_gl))) return rc;
-    if ((rc = stage_in(c, c->st[19], target_lens, (size_t)n_target_total, &d_tl))) return rc;
-    if ((rc = stage_out(c, c->st[20], (size_t)n_units, &d_calls))) return rc;
-    if ((rc = stage_out(c, c->st[21], marg_n, &d_marg))) return rc;
-    if ((rc = stage_in(c, c->st[22], joint_off, (size_t)n_units + 1, &d_joff))) return rc;
-    if ((rc = stage_out(c, c->st[23], joint_len, &d_joint))) return rc;
-    if ((rc = stage_out(c, c->st[24], (size_t)n_units, &d_jn))) return rc;
-    if ((rc = stage_out(c, c->st[25], (size_t)n_units, &d_jt))) return rc;
-    if ((rc = stage_in(c, c->st[26], (const int32_t*)unit_task.data(), (size_t)n_units, &d_task))) return rc;
-    if ((rc = stage_in(c, c->st[27], unit_word_off, (size_t)n_units + 1, &d_uw))) return rc;
-    if ((rc = stage_in(c, c->st[28], unit_seq4_off, (size_t)n_units + 1, &d_us))) return rc;
-    if ((rc = stage_in(c, c->st[29], unit_name_off, (size_t)n_units + 1, &d_un))) return rc;
-    if ((rc = stage_out(c, c->st[30], s4_bytes, &d_seq4))) return rc;
-    if ((rc = stage_out(c, c->st[31], (size_t)n_reads + 1, &d_s4off))) return rc;
-    if ((rc = stage_out(c, c->st[32], nm_bytes, &d_names))) return rc;
-    if ((rc = stage_out(c, c->st[33], (size_t)n_reads + 1, &d_nmoff))) return rc;
+    const std::vector<Staged> list = {
+        arr_scratch(d_packed, (size_t)unit_word_off[n_units]), arr_scratch(d_off, n + 1), arr_out(d_len, read_len, n),
+        arr_in(d_uoff, unit_read_off, nu + 1), arr_in(d_ulad, unit_ladder, nu),
+        arr_out(d_tag, out_tag, n), arr_out(d_h, out_h, n), arr_out(d_score, out_score, n),
+        arr_scratch(d_f, hn), arr_scratch(d_p, hn), arr_out(d_r, rept_cnt, hn),       // (rept_cnt: copied back where the caller passed it)
+        arr_in(d_units, units, nu), arr_in(d_gl, global_lens, (size_t)n_global_total), arr_in(d_tl, target_lens, (size_t)n_target_total),
+        arr_out(d_calls, calls, nu), arr_out(d_marg, marg, nu * 2 * marg_stride),
+        arr_in(d_joff, joint_off, nu + 1), arr_out(d_joint, joint, (size_t)joint_off[n_units] * 3), arr_out(d_jn, joint_n, nu), arr_out(d_jt, joint_total, nu),
+        arr_in(d_task, (const int32_t*)unit_task.data(), nu), arr_in(d_uw, unit_word_off, nu + 1), arr_in(d_us, unit_seq4_off, nu + 1), arr_in(d_un, unit_name_off, nu + 1),
+        // (room for n + 1 offsets; without reads nothing comes back and the caller may pass neither seq4_off nor name_off)
+        arr_out(d_seq4, seq4, (size_t)unit_seq4_off[n_units]), arr_out(d_s4off, seq4_off, n + 1, offs),
+        arr_out(d_names, (uint8_t*)names, (size_t)unit_name_off[n_units]), arr_out(d_nmoff, name_off, n + 1, offs),
+    };
+    rc = stage(c, list);
     g = 0;
-    for (int32_t sgi = 0; sgi < n_segs; ++sgi) {
-        HIPCHK(c, tredgpu_front::launch_pack_selected(views[sgi].out, views[sgi].sel_list, d_task, d_uoff, d_uw, d_us, d_un, g, segs[sgi].n_units, d_packed,
-                                                      d_off, d_len, d_seq4, d_s4off, d_names, d_nmoff, c->stream));
+    for (int32_t sgi = 0; sgi < n_segs && !rc; ++sgi) {
+        rc = HIPRC(c, tredgpu_front::launch_pack_selected(views[sgi].out, views[sgi].sel_list, d_task, d_uoff, d_uw, d_us, d_un, g, segs[sgi].n_units, d_packed,
+                                                          d_off, d_len, d_seq4, d_s4off, d_names, d_nmoff, c->stream));
         g += segs[sgi].n_units;
     }
-    if (n_reads > 0 && (rc = run_sw_device(c, d_packed, d_off, d_len, n_reads, d_uoff, d_ulad, n_units, params, max_len, d_tag, d_h, d_score, nullptr, 0)))
-        return rc;
-    {
-        ScopedTimer tm(c, TREDGPU_KERNEL_TALLY);
-        HIPCHK(c, launch_tally(d_tag, d_h, n_reads, d_uoff, n_units, nullptr, hist_stride, d_f, d_p, d_r, (uint8_t*)c->ws_drop.p, c->stream));
-    }
-    if ((rc = run_grid_device(c, d_units, n_units, hist_stride, d_f, d_p, d_r, d_gl, d_tl, d_calls, nullptr, nullptr, d_marg, marg_stride, limits, d_joff,
-                              d_joint, d_jn, d_jt)))
-        return rc;
-    if ((rc = copy_back(c, out_tag, (const uint8_t*)d_tag, (size_t)n_reads))) return rc;
-    if ((rc = copy_back(c, out_h, (const int16_t*)d_h, (size_t)n_reads))) return rc;
-    if ((rc = copy_back(c, out_score, (const int16_t*)d_score, (size_t)n_reads))) return rc;
-    if ((rc = copy_back(c, rept_cnt, (const int32_t*)d_r, rept_cnt ? hn : 0))) return rc;
-    if ((rc = copy_back(c, joint, (const double*)d_joint, joint_len))) return rc;
-    if ((rc = copy_back(c, joint_n, (const int32_t*)d_jn, (size_t)n_units))) return rc;
-    if ((rc = copy_back(c, joint_total, (const double*)d_jt, (size_t)n_units))) return rc;
-    if ((rc = copy_back(c, calls, (const tredgpu_call*)d_calls, (size_t)n_units))) return rc;
-    if ((rc = copy_back(c, marg, (const double*)d_marg, marg_n))) return rc;
-    if ((rc = copy_back(c, read_len, (const int32_t*)d_len, (size_t)n_reads))) return rc;
-    if ((rc = copy_back(c, seq4_off, (const int64_t*)d_s4off, n_reads > 0 ? (size_t)n_reads + 1 : 0))) return rc;
-    if ((rc = copy_back(c, seq4, (const uint8_t*)d_seq4, s4_bytes))) return rc;
-    if ((rc = copy_back(c, name_off, (const int64_t*)d_nmoff, n_reads > 0 ? (size_t)n_reads + 1 : 0))) return rc;
-    if ((rc = copy_back(c, (uint8_t*)names, (const uint8_t*)d_names, nm_bytes))) return rc;
-    HIPCHK(c, stream_sync(c));
-    return 0;
+    if (!rc) rc = run_fused_device(c, d_packed, d_off, d_len, n_reads, d_uoff, d_ulad, d_units, n_units, params, params->max_read_len,
+                                   nullptr, d_gl, d_tl, d_tag, d_h, d_score, hist_stride, d_f, d_p, d_r, d_calls, d_marg, marg_stride,
+                                   limits, d_joff, d_joint, d_jn, d_jt);
+    return finish(c, list, rc);
 }
 
 int tredgpu_genotype_batch(tredgpu_ctx* c, int mem, const uint32_t* packed, const int64_t* read_off,
@@ -1167,16 +1117,9 @@ int tredgpu_genotype_batch(tredgpu_ctx* c, int mem, const uint32_t* packed, cons
         int limits[2] = {0, 0};
         if (n_units > 0 && (rc = query_max_insert(c, units, n_units, limits))) return rc;
         if (read_pair_id && (rc = ensure(c, c->ws_drop, (size_t)n_reads))) return rc;
-        if ((rc = run_sw_device(c, packed, read_off, read_len, n_reads, unit_read_off, unit_ladder, n_units, params,
-                                max_len, out_tag, out_h, out_score, nullptr, 0)))
-            return rc;
-        {
-            ScopedTimer tm(c, TREDGPU_KERNEL_TALLY);
-            HIPCHK(c, launch_tally(out_tag, out_h, n_reads, unit_read_off, n_units, read_pair_id, hist_stride, full_cnt,
-                                   pref_cnt, rept_cnt, (uint8_t*)c->ws_drop.p, c->stream));
-        }
-        return run_grid_device(c, units, n_units, hist_stride, full_cnt, pref_cnt, rept_cnt, global_lens, target_lens,
-                               calls, nullptr, nullptr, nullptr, 0, limits);
+        return run_fused_device(c, packed, read_off, read_len, n_reads, unit_read_off, unit_ladder, units, n_units, params, max_len,
+                                read_pair_id, global_lens, target_lens, out_tag, out_h, out_score, hist_stride, full_cnt, pref_cnt,
+                                rept_cnt, calls, nullptr, 0, limits);
     }
     if (mem != TREDGPU_MEM_HOST) return fail(c, -2, "bad mem");
     // HOST memory: compose the three host-memory calls (each validates and stages its own arguments)
