@@ -108,6 +108,13 @@ COHORT_CHUNK = 1024             # TREDGPU_COHORT_CHUNK: incidence entries of an 
 COHORT_LONG_LIST = 1024         # TREDGPU_COHORT_LONG_LIST: a sample of more pairs has a workgroup to itself, any other a wavefront
 COHORT_ITERS, COHORT_ALPHA, COHORT_TOL = 64, 1.0, 1e-6     # EM iterations, pseudo-chromosomes, what `converged` reports: a choice
 
+# the tandem-repeat scan's symbols (include/tredscan.h)
+SCAN_EXPORTS = ("tredscan_scan", "tredscan_get_timing", "tredscan_reset_timing", "tredscan_release", "tredscan_last_error")
+SCAN_MAX_PERIOD = 6             # TREDSCAN_MAX_PERIOD
+SCAN_TILE = 4096                # TREDSCAN_TILE: the letters one wavefront owns
+SCAN_MAX_LETTERS = 1 << 30      # TREDSCAN_MAX_LETTERS: the letters of all segments of one call
+SCAN_MIN_COPIES = (10, 6, 5, 4, 4, 4)      # whole copies a run of period 1 .. 6 needs to be reported: a choice, not a measurement
+
 # every symbol include/tredgpu.h declares (tests check the .so exports them all)
 EXPORTS = ("tredgpu_create", "tredgpu_destroy", "tredgpu_last_error", "tredgpu_sync", "tredgpu_get_stream",
            "tredgpu_version", "tredgpu_set_ladders", "tredgpu_set_model", "tredgpu_pack_reads",
@@ -127,6 +134,7 @@ KERNEL_SECOND = 18              # tredsecond_get_timing (include/tredsecond.h): 
 KERNEL_PILEUP = 19              # tredpileup_get_timing (include/tredpileup.h): calls of pileup and their device time
 KERNEL_TRIO = 20                # tredtrio_get_timing (include/tredtrio.h): calls of trio and their device time
 KERNEL_COHORT = 21              # tredcohort_get_timing (include/tredcohort.h): calls of cohort and their device time
+KERNEL_SCAN = 22                # tredscan_get_timing (include/tredscan.h): calls of scan and their device time
 
 
 # the timed opt-in units: (prefix, get-timing, reset-timing, KERNEL_* selector, last_error), in the order reset_timing has
@@ -138,7 +146,8 @@ SIDE_UNITS = (("tredlong", "tredlong_cigar_timing", "tredlong_cigar_reset_timing
               ("tredsecond", "tredsecond_get_timing", "tredsecond_reset_timing", KERNEL_SECOND, "tredsecond_last_error"),
               ("tredpileup", "tredpileup_get_timing", "tredpileup_reset_timing", KERNEL_PILEUP, "tredpileup_last_error"),
               ("tredtrio", "tredtrio_get_timing", "tredtrio_reset_timing", KERNEL_TRIO, "tredtrio_last_error"),
-              ("tredcohort", "tredcohort_get_timing", "tredcohort_reset_timing", KERNEL_COHORT, "tredcohort_last_error"))
+              ("tredcohort", "tredcohort_get_timing", "tredcohort_reset_timing", KERNEL_COHORT, "tredcohort_last_error"),
+              ("tredscan", "tredscan_get_timing", "tredscan_reset_timing", KERNEL_SCAN, "tredscan_last_error"))
 
 _lib = None
 
@@ -175,6 +184,7 @@ def load():
                                              vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.tredtrio_evaluate.argtypes = [vp, C.POINTER(TrioParams), i64] + [vp] * 19
     lib.tredcohort_evaluate.argtypes = [vp, C.POINTER(CohortParams), i64] + [vp] * 16
+    lib.tredscan_scan.argtypes = [vp, vp, vp, i32, vp, i64, vp, vp, vp, vp, C.POINTER(i64)]
     for prefix, get_timing, reset_timing, _, last_error in SIDE_UNITS:
         getattr(lib, get_timing).argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
         getattr(lib, reset_timing).argtypes = [vp]
@@ -735,6 +745,29 @@ class Context:
                                           _ptr(out_n_alleles), _ptr(out_alleles), _ptr(out_freq), _ptr(out_count), _ptr(out_trace),
                                           _ptr(out_sample_call), _ptr(out_sample_values), _ptr(out_r))
         self._chk_side(rc, "tredcohort_evaluate failed ({})".format(rc), self.lib.tredcohort_last_error)
+
+    def scan(self, letters, seg_off, min_copies=SCAN_MIN_COPIES, cap=1 << 16):
+        """tredscan_scan (include/tredscan.h): the tandem repeats of the segments seg_off (int64 [n_seg + 1]) of letters
+        (bytes or a uint8 array), host memory.  min_copies: the whole copies a run of period 1 .. 6 needs, 0 for a period
+        that is off.  Returns (seg int32, start int64, length int32, period int32, total): the first min(total, cap)
+        records in ascending (seg, start, period) order; total is what there is, also above cap."""
+        buf = np.frombuffer(letters, np.uint8) if not isinstance(letters, np.ndarray) else letters
+        off = np.ascontiguousarray(seg_off, np.int64)
+        mc = np.ascontiguousarray(min_copies, np.int32)
+        if buf.dtype != np.uint8 or off.ndim != 1 or len(off) < 1 or mc.shape != (SCAN_MAX_PERIOD,):
+            raise ValueError("scan: letters are bytes, seg_off has n_seg + 1 entries, min_copies has {}".format(SCAN_MAX_PERIOD))
+        if len(buf) < off[-1]:
+            raise ValueError("scan: seg_off ends at {} but there are {} letters".format(int(off[-1]), len(buf)))
+        cap = int(cap)
+        room = max(cap, 0)
+        seg, start = np.empty(room, np.int32), np.empty(room, np.int64)
+        length, period = np.empty(room, np.int32), np.empty(room, np.int32)
+        total = C.c_int64(0)
+        rc = self.lib.tredscan_scan(self.h, _ptr(buf) if len(buf) else None, _ptr(off), len(off) - 1, _ptr(mc), cap, _ptr(seg),
+                                    _ptr(start), _ptr(length), _ptr(period), C.byref(total))
+        self._chk_side(rc, "tredscan_scan failed ({})".format(rc), self.lib.tredscan_last_error)
+        n = min(total.value, room)
+        return seg[:n], start[:n], length[:n], period[:n], total.value
 
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")

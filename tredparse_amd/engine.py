@@ -786,6 +786,16 @@ class Engine(object):
         _refuse_item("cohort", refused, _lib.COHORT_OK, np.zeros(n, np.int64), np.arange(n), np.zeros(n, np.int64))
         return results_of(n, item_off, samples, ploidy, allele_off, members, out, tol)
 
+    # ---- where the repeats are ----------------------------------------------------------------------
+    def scan_repeats(self, segments, min_copies=None, periods=None):
+        """The perfect tandem repeats of `segments` (bytes-like letter sequences) on this engine's context, as (seg, start,
+        length, period) arrays in ascending (seg, start, period) order: prepare.scan_repeats, which batches the segments
+        into Context.scan calls and joins the runs of a segment longer than one call (the definition: DESIGN.md 4,
+        "Tandem-repeat scan").  min_copies: per period 1 .. 6, _lib.SCAN_MIN_COPIES by default -- a choice, not a
+        measurement; periods: the periods to report, all by default."""
+        from .prepare import scan_repeats
+        return scan_repeats(self.ctx, segments, min_copies=min_copies, periods=periods)
+
     # ---- the whole path ------------------------------------------------------------------------------
     def genotype(self, units, want_grid=True):
         """SW + tagging -> histograms -> likelihood grid for a batch of units (a list of Unit, or a PackedUnits); returns

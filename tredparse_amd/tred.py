@@ -78,13 +78,23 @@ class _AlsoConsensus(argparse.Action):
         namespace.consensus = True
 
 
-def set_argparse():
-    names = sorted(TREDsRepo().names)
+def _sites_of(argv):
+    """--sites of a command line, before the parser proper exists: its --tred choices depend on the directory."""
+    pre = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    pre.add_argument("--sites", default="sites")
+    return pre.parse_known_args(list(argv or []))[0].sites
+
+
+def set_argparse(argv=None):
+    names = sorted(TREDsRepo(sites=_sites_of(argv)).names)
     p = _Parser(prog="tred.py", description=__doc__.split("\n\n")[0],
                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("infile", nargs="?", help="a BAM, a text file listing BAMs, or a CSV of samplekey,bam[,locus]")
     p.add_argument("--ref", choices=BUILDS, default="hg38", help="genome build the BAMs are aligned to")
     p.add_argument("--tred", action="append", choices=names, default=None, help="locus to call (repeatable); all if omitted")
+    p.add_argument("--sites", default="sites", metavar="DIR",
+                   help="directory of *.json files of user loci in the reference's site schema, loaded beside the built-in table "
+                        "(python -m tredparse_amd.prepare writes them)")
     p.add_argument("--haploid", action="append", help="contig to treat as haploid (repeatable)")
     p.add_argument("--useclippedreads", action="store_true", help="count clipped reads as evidence")
     p.add_argument("--long-reads", dest="long_reads", action="store_true",
@@ -932,7 +942,7 @@ def _cohort_pass(args, keys, repo, loci, engine=None):
 
 def main(args, quiet=False):
     argv = list(args)
-    p = set_argparse()
+    p = set_argparse(argv)
     args = p.parse_args(argv)
     if args.pedigree and args.no_output:
         p.error("--pedigree reads the samples' files: it cannot go with --no-output")
@@ -972,7 +982,7 @@ def main(args, quiet=False):
     else:
         samples = read_csv(infile, args)       # paths become absolute here, before the working directory changes
     cwd = os.getcwd()
-    sites = os.path.join(cwd, "sites")
+    sites = os.path.join(cwd, args.sites)       # (the option is in a --gpus child's command line as it is in this one)
     os.makedirs(args.workdir, exist_ok=True)
     os.chdir(args.workdir)
     try:
