@@ -40,7 +40,7 @@ struct tredgpu_ctx {
     Buf d_model;
     bool have_model = false;
     // workspaces (grow-only, reused across calls)
-    Buf ws_quads, ws_counter, ws_drop, ws_grid, ws_stats, ws_perm, ws_class, ws_gdesc, ws_gtile, ws_gctr, ws_ucnt, ws_bins, ws_kde;
+    Buf ws_quads, ws_counter, ws_drop, ws_grid, ws_stats, ws_perm, ws_class, ws_gdesc, ws_gtile, ws_gctr, ws_ucnt, ws_bins, ws_kde, ws_best, ws_cnt;
     int* h_pin = nullptr;  // pinned word for small read-backs
     hipEvent_t sync_ev = nullptr;  // stream_sync's event
     size_t grid_pool_bytes = GRID_POOL_BYTES;   // TREDGPU_GRID_POOL_MB overrides (tuning / tests of the multi-pass path)
@@ -391,7 +391,7 @@ void tredgpu_destroy(tredgpu_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)stream_sync(c);
     for (Buf* b : {&c->d_ladders, &c->d_seq, &c->d_model, &c->ws_quads, &c->ws_counter, &c->ws_drop,
-                   &c->ws_grid, &c->ws_stats, &c->ws_perm, &c->ws_class, &c->ws_gdesc, &c->ws_gtile, &c->ws_gctr, &c->ws_ucnt, &c->ws_bins, &c->ws_kde})
+                   &c->ws_grid, &c->ws_stats, &c->ws_perm, &c->ws_class, &c->ws_gdesc, &c->ws_gtile, &c->ws_gctr, &c->ws_ucnt, &c->ws_bins, &c->ws_kde, &c->ws_best, &c->ws_cnt})
         release(*b);
     for (Buf& b : c->st) release(b);
     for (auto& t : c->timers)
@@ -633,22 +633,38 @@ static int run_sw_device(tredgpu_ctx* c, const uint32_t* packed, const int64_t* 
     a.perm = (const int32_t*)c->ws_perm.p;
     if ((rc = ensure(c, c->ws_ucnt, sw_unit_cnt_bytes(n_units)))) return rc;
     if ((rc = ensure(c, c->ws_bins, sw_bin_bytes(n_ladders)))) return rc;
-    HIPCHK(c, launch_build_quads(a, (uint8_t*)c->ws_class.p, (int32_t*)c->ws_perm.p, (Quad*)c->ws_quads.p,
-                                 (int32_t*)c->ws_counter.p, (int32_t*)c->ws_ucnt.p, (int32_t*)c->ws_bins.p, n_ladders,
-                                 max_quads, c->stream));
+    if ((rc = ensure(c, c->ws_best, (size_t)n_reads * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(c, c->ws_cnt, (size_t)n_reads * sizeof(int32_t)))) return rc;
+    a.best = (int32_t*)c->ws_best.p;
     if (c->ws_stats.p == nullptr) {
         if ((rc = ensure(c, c->ws_stats, SW_STAT_SLOTS * 8 * sizeof(unsigned long long)))) return rc;
         HIPCHK(c, hipMemsetAsync(c->ws_stats.p, 0, SW_STAT_SLOTS * 8 * sizeof(unsigned long long), c->stream));
     }
     a.stats = (unsigned long long*)c->ws_stats.p;
+    const int rows = rows_for(max_len);
+    auto build_quads = [&](int pass) {
+        return launch_build_quads(a, pass, rows, (uint8_t*)c->ws_class.p, (int32_t*)c->ws_cnt.p, (int32_t*)c->ws_perm.p,
+                                  (Quad*)c->ws_quads.p, (int32_t*)c->ws_counter.p, (int32_t*)c->ws_ucnt.p,
+                                  (int32_t*)c->ws_bins.p, n_ladders, max_quads, c->stream);
+    };
+    HIPCHK(c, build_quads(0));
     {
+        // one record per call: both launches and the re-pack between them
         ScopedTimer tm(c, TREDGPU_KERNEL_SW);
         // a branch (suffix, or prefix on the reverse strand) long enough to pass the score filter of 30 by itself
         // needs the kernel variant that also sweeps the branch alone
         bool generic = false;
-        for (const LadderDesc& d : c->h_ladders)
+        bool two_strands = false;
+        for (const LadderDesc& d : c->h_ladders) {
             for (int s2 = 0; s2 < d.n_strands; ++s2) generic = generic || (d.max_units > 0 && d.blen[s2] * p->match >= 30);
-        HIPCHK(c, launch_sw_ladder(a, rows_for(max_len), generic, max_quads, c->stream));
+            two_strands = two_strands || d.n_strands >= 2;
+        }
+        HIPCHK(c, launch_sw_ladder(a, rows, generic, max_quads, c->stream));
+        // strand 1 for the reads still open after strand 0 (the dump's single launch swept both)
+        if (out_dump == nullptr && two_strands) {
+            HIPCHK(c, build_quads(1));
+            HIPCHK(c, launch_sw_ladder(a, rows, generic, max_quads, c->stream));
+        }
     }
     return 0;
 }

@@ -526,9 +526,14 @@ __global__ __launch_bounds__(64, W) void sw_cont_kernel(SwArgs a) {
     const bool valid = job < q_count;
     int L, row0;
     bool too_long;
+    // arg-max so far, one word: (score << 9 | 511 - units) << 3 | tag; -1 = nothing yet.  A candidate must beat
+    // it on (score, -units): max(res, key=(score, -units)), first maximal element in db order (bam_parser.py:174).
+    // It travels in a.best from the launch that sweeps strand 0 to the one that sweeps strand 1 (read_class_kernel: -1).
+    int best;
     {
         const int64_t rd = valid ? (int64_t)a.perm[q_first + job] : 0;
         L = valid ? a.read_len[rd] : 0;
+        best = valid ? a.best[rd] : -1;
         too_long = L > 16 * R;  // not representable in this instantiation: flagged, not aligned
         if (too_long) L = 0;
         row0 = jl * R;
@@ -550,9 +555,6 @@ __global__ __launch_bounds__(64, W) void sw_cont_kernel(SwArgs a) {
     // REPT cut-off: per-read ceil(L/period) with --useclippedreads, else the ladder's (bam_parser.py:154-155)
     const int mu_rept = a.p.clip ? (L + period - 1) / period : max_units;
 
-    // arg-max so far, one word: (score << 9 | 511 - units) << 3 | tag; -1 = nothing yet.  A candidate must beat
-    // it on (score, -units): max(res, key=(score, -units)), first maximal element in db order (bam_parser.py:174)
-    int best = -1;
     // wave-uniform work counters, packed so that they cost two scalar registers and never a scratch slot:
     // cnt_cols = trunk columns | continuation columns << 16;  cnt_ends = combined | dropped << 8 | from trunk << 16
     // (a strand has at most 511 columns and 127 templates)
@@ -900,26 +902,55 @@ __global__ __launch_bounds__(64, W) void sw_cont_kernel(SwArgs a) {
         a.out_tag[rd] = (uint8_t)bestTag;
         a.out_h[rd] = (int16_t)(bestTag == TREDGPU_TAG_NONE ? 0 : bestU);
         a.out_score[rd] = (int16_t)(bestTag == TREDGPU_TAG_NONE ? 0 : bestS);
+        a.best[rd] = best;
     }
 }
 
 // Strand classes and quad formation.  The exact 6-mer strand filter (see sw_cont_kernel) is evaluated per read
 // here, once: bit s of the class = "strand s can reach the score filter for this read".  Reads that need no strand
-// at all are finished on the spot (no candidate: tag NONE).  The others are packed four to a wavefront by
-// (ladder, class, level) across the units of a batch -- a read's alignment does not depend on its wave-mates, so
-// only the last quad of each bin can be partial (per-unit packing left 7 % of the read slots of the bench batch
-// empty).  The level is the read's count of 6-mers present in the templates, in steps of 6 (32 levels): that count caps the
-// read's score, a template of length T needs a score of min(L, T)/2, so reads of one level stop needing the
-// trunk at about the same template and the wave can leave the strand together (strand exit in sw_cont_kernel).
-// Bin b = (3 * ladder + k) * SW_LEVELS + level holds class {1, 3, 2}[k].
-//   read_class_kernel   classes and levels, bin totals, each unit's offset inside its bins (one atomic per unit and bin)
+// at all are finished on the spot (no candidate: tag NONE).
+//
+// Two passes.  The strands are swept in two launches: pass A sweeps strand 0 for every read whose class has bit 0,
+// pass B strand 1 for every read whose class has bit 1 and that is still open after pass A -- repack_kernel applies the
+// SW kernel's own entry test (6-mer threshold, still_open with the read's arg-max so far) to each read, so a read that
+// strand 0 has settled no longer rides through strand 1 because a wave-mate is still open.  The arg-max word travels
+// in SwArgs::best.  Nothing a read computes depends on its wave-mates and strand 0 still comes first, so the results
+// are those of one launch.  The per-template dump keeps the single launch (quads of both strands, no pass B).
+//
+// In each pass the reads are packed four to a wavefront by (ladder, level) across the units of a batch -- only the
+// last quad of each bin can be partial (per-unit packing left 7 % of the read slots of the bench batch empty).  The
+// level is the read's count of 6-mers present in the templates of the strand being swept, in steps of 6 (32 levels):
+// that count caps the read's score, a template of length T needs a score of min(L, T)/2, so reads of one level stop
+// needing the trunk at about the same template and the wave can leave the strand together (strand exit in
+// sw_cont_kernel).  Bin b = ladder * SW_LEVELS + (31 - level): within a ladder the high levels -- the long quads -- are
+// handed out first, and the launch's tail is made of short ones.  A read's bin in the pass being formed is its key
+// (KEY_NONE: not part of the pass).
+//   read_class_kernel   pass A: counts, keys, bin totals, each unit's offset inside its bins (one atomic per unit and bin)
+//   repack_kernel       pass B: the same from the stored counts and the arg-max after pass A
 //   bin_scan_kernel     bin -> first slot in the permutation / first quad; the quad count of the launch
 //   scatter_kernel      each unit writes its reads' indices into its runs of the bins
 //   fill_quads_kernel   one thread per quad: its bin by binary search over the quad offsets
 constexpr int BIN_STRIDE = 16;   // ints: every bin counter on its own 64-byte line
 constexpr int SW_LEVELS = 32;
-constexpr int UNIT_BINS = 3 * SW_LEVELS;   // bins one unit can feed
-__device__ __forceinline__ int class_slot(int cls) { return cls == 1 ? 0 : (cls == 3 ? 1 : 2); }
+constexpr int UNIT_BINS = SW_LEVELS;   // bins one unit can feed in one pass
+constexpr int KEY_NONE = 0xFF;
+constexpr int CNT_UNFILTERED = 0x7FFF;   // stored 6-mer count of a read the filter does not apply to
+__device__ __forceinline__ int level_key(int cnt) { return SW_LEVELS - 1 - min(SW_LEVELS - 1, cnt / 6); }
+__device__ __forceinline__ int kmer_threshold(const tredgpu_sw_params& p) {
+    // 6-mer filter premise: every run break costs >= 5 matches (see sw_cont_kernel)
+    return min(p.mismatch, p.gap_open) >= 5 * p.match ? (30 + p.match - 1) / p.match - 5 : 0;
+}
+
+// The unit's histogram over its bins -> bin totals; the unit's run inside each of its bins starts where the bin's
+// total stood when the unit arrived.
+__device__ __forceinline__ void claim_bin_runs(const int* hist, int lad, int g, int32_t* unit_cnt, int32_t* bin_total) {
+    for (int k = threadIdx.x; k < UNIT_BINS; k += (int)blockDim.x) {
+        const int n = hist[k];
+        int at = 0;
+        if (n) at = atomicAdd(bin_total + ((size_t)lad * UNIT_BINS + k) * BIN_STRIDE, n);
+        unit_cnt[(size_t)g * UNIT_BINS + k] = at;
+    }
+}
 
 // The read's 6-mers present in the two strands' template bitmaps (windows with an N count as present).  `rec` = the
 // read's packed record, bm = the two 128-word bitmaps (LDS).  One word of 16 bases per trip: the
@@ -959,14 +990,17 @@ __device__ __forceinline__ void kmer_counts(const uint32_t* rec, int L, const ui
     }
 }
 
-__global__ __launch_bounds__(64) void read_class_kernel(SwArgs a, uint8_t* read_class, int32_t* unit_cnt, int32_t* bin_total) {
+// read_cnt[rd] = cnt0 | cnt1 << 16: the read's 6-mer counts on the two strands (CNT_UNFILTERED where the filter does not
+// apply), kept for repack_kernel.  A read outside pass A gets tag NONE here; pass B overwrites it if the read gets there.
+__global__ __launch_bounds__(64) void read_class_kernel(SwArgs a, uint8_t* read_key, int32_t* read_cnt, int32_t* unit_cnt,
+                                                          int32_t* bin_total) {
     const int g = blockIdx.x;
     if (g >= a.n_units) return;
     // (device-resident unit tables are not validated by the host: keep a bad index from leaving the tables)
     const int lad = min(max(a.unit_ladder[g], 0), a.n_ladders - 1);
     const LadderDesc* ld = a.ladders + lad;
     const bool full_dump = a.out_dump != nullptr;
-    const int thr = min(a.p.mismatch, a.p.gap_open) >= 5 * a.p.match ? (30 + a.p.match - 1) / a.p.match - 5 : 0;
+    const int thr = kmer_threshold(a.p);
     const bool filt = !full_dump && thr > 0 && ld->kmer_ok != 0 && ld->max_units > 0;
     const int r0 = a.unit_read_off[g], r1 = a.unit_read_off[g + 1];
     // the two 4096-bit presence maps of the ladder, in LDS: every base of every read looks both up, and a
@@ -979,32 +1013,71 @@ __global__ __launch_bounds__(64) void read_class_kernel(SwArgs a, uint8_t* read_
     for (int k = threadIdx.x; k < UNIT_BINS; k += (int)blockDim.x) hist[k] = 0;
     __syncthreads();
     for (int rd = r0 + (int)threadIdx.x; rd < r1; rd += (int)blockDim.x) {
-        int cls = ld->n_strands >= 2 ? 3 : 1;
-        int level = SW_LEVELS - 1;
+        int cnt0 = CNT_UNFILTERED, cnt1 = CNT_UNFILTERED;
         const int L = a.read_len[rd];
-        if (filt && L <= a.max_rows) {   // over-long reads go to the SW kernel, which flags them
-            int cnt0, cnt1;
-            kmer_counts(a.packed + a.read_off[rd], L, &bm[0][0], cnt0, cnt1);
-            cls = (cnt0 >= thr ? 1 : 0) | (cnt1 >= thr ? 2 : 0);
-            level = min(SW_LEVELS - 1, max(cls & 1 ? cnt0 : 0, cls & 2 ? cnt1 : 0) / 6);
-        }
-        read_class[rd] = (uint8_t)(cls | level << 2);
-        if (cls == 0) {   // no strand can produce a candidate: bam_parser.py:171-172 "if not res: return"
+        // over-long reads go to the SW kernel, which flags them (in pass A: unfiltered reads have bit 0)
+        if (filt && L <= a.max_rows) kmer_counts(a.packed + a.read_off[rd], L, &bm[0][0], cnt0, cnt1);
+        read_cnt[rd] = cnt0 | cnt1 << 16;
+        a.best[rd] = -1;
+        if (cnt0 >= thr) {
+            const int key = level_key(cnt0);
+            read_key[rd] = (uint8_t)key;
+            atomicAdd(&hist[key], 1);
+        } else {
+            // strand 0 cannot produce a candidate; if strand 1 cannot either (or pass B finds nothing), that is
+            // bam_parser.py:171-172 "if not res: return"
+            read_key[rd] = (uint8_t)KEY_NONE;
             a.out_tag[rd] = TREDGPU_TAG_NONE;
             a.out_h[rd] = 0;
             a.out_score[rd] = 0;
-        } else {
-            atomicAdd(&hist[class_slot(cls) * SW_LEVELS + level], 1);
         }
     }
     __syncthreads();
-    for (int k = threadIdx.x; k < UNIT_BINS; k += (int)blockDim.x) {
-        // the unit's run inside each of its bins starts where the bin's total stood when the unit arrived
-        const int n = hist[k];
-        int at = 0;
-        if (n) at = atomicAdd(bin_total + ((size_t)lad * UNIT_BINS + k) * BIN_STRIDE, n);
-        unit_cnt[(size_t)g * UNIT_BINS + k] = at;
+    claim_bin_runs(hist, lad, g, unit_cnt, bin_total);
+}
+
+// Pass B's reads: class bit 1 (the stored count against the threshold) and the entry test sw_cont_kernel makes for
+// strand 1 -- the same cap, the same still_open(first template) with the arg-max pass A left.  Never stricter than the
+// kernel's, which keeps its tests: a read that gets here is handled as in a single launch.  kcap_in_kernel: the
+// instantiation that will run derives a score cap from the 6-mer count (5 <= R <= 11).
+__global__ __launch_bounds__(64) void repack_kernel(SwArgs a, uint8_t* read_key, const int32_t* read_cnt, int32_t* unit_cnt,
+                                                      int32_t* bin_total, int kcap_in_kernel) {
+    const int g = blockIdx.x;
+    if (g >= a.n_units) return;
+    const int lad = min(max(a.unit_ladder[g], 0), a.n_ladders - 1);
+    const LadderDesc* ld = a.ladders + lad;
+    const int thr = kmer_threshold(a.p);
+    const bool with_kcap = kcap_in_kernel && thr > 0 && ld->kmer_ok != 0;
+    const bool two_strands = ld->n_strands >= 2;
+    const int first_T = ld->alen[1] + ld->period * (ld->max_units > 0 ? 1 : 0) + ld->blen[1];
+    const int r0 = a.unit_read_off[g], r1 = a.unit_read_off[g + 1];
+    __shared__ int hist[UNIT_BINS];
+    __shared__ int n_pass;
+    for (int k = threadIdx.x; k < UNIT_BINS; k += (int)blockDim.x) hist[k] = 0;
+    if (threadIdx.x == 0) n_pass = 0;
+    __syncthreads();
+    for (int rd = r0 + (int)threadIdx.x; rd < r1; rd += (int)blockDim.x) {
+        const int L = a.read_len[rd];
+        const int cnt1 = (int)((uint32_t)read_cnt[rd] >> 16);
+        const bool counted = cnt1 != CNT_UNFILTERED;
+        const int kcap = with_kcap && counted ? (cnt1 + 5) * a.p.match : 1 << 20;
+        const int cap = min(kcap, L * a.p.match);
+        const int min_score = max(min(L, first_T) >> 1, 30);
+        const bool open = max(min_score, (a.best[rd] >> 12) + 1) <= cap;
+        // (an over-long read was flagged in pass A: it is unfiltered, and unfiltered reads have bit 0)
+        const bool go = two_strands && L <= a.max_rows && cnt1 >= thr && open;
+        int key = KEY_NONE;
+        if (go) {
+            key = level_key(cnt1);
+            atomicAdd(&hist[key], 1);
+            atomicAdd(&n_pass, 1);
+        }
+        read_key[rd] = (uint8_t)key;
     }
+    __syncthreads();
+    claim_bin_runs(hist, lad, g, unit_cnt, bin_total);
+    if (threadIdx.x == 0 && a.stats != nullptr && n_pass)   // counter 7: reads handed to pass B
+        atomicAdd(a.stats + (size_t)(g & (SW_STAT_SLOTS - 1)) * 8 + 7, (unsigned long long)n_pass);
 }
 
 // bins[b * BIN_STRIDE + 0] total reads, +1 first permutation slot, +2 first quad.
@@ -1039,7 +1112,7 @@ __global__ __launch_bounds__(1024) void bin_scan_kernel(int32_t* bins, int n_bin
     }
 }
 
-__global__ __launch_bounds__(64) void scatter_kernel(SwArgs a, const uint8_t* read_class, const int32_t* unit_cnt, int32_t* bins,
+__global__ __launch_bounds__(64) void scatter_kernel(SwArgs a, const uint8_t* read_key, const int32_t* unit_cnt, int32_t* bins,
                                                        int32_t* perm) {
     const int g = blockIdx.x;
     if (g >= a.n_units) return;
@@ -1050,12 +1123,14 @@ __global__ __launch_bounds__(64) void scatter_kernel(SwArgs a, const uint8_t* re
     __syncthreads();
     const int r0 = a.unit_read_off[g], r1 = a.unit_read_off[g + 1];
     for (int r = r0 + (int)threadIdx.x; r < r1; r += (int)blockDim.x) {
-        const int c = read_class[r] & 3, level = read_class[r] >> 2;
-        if (c != 0) perm[atomicAdd(&pos[class_slot(c) * SW_LEVELS + level], 1)] = r;
+        const int key = read_key[r];
+        if (key != KEY_NONE) perm[atomicAdd(&pos[key], 1)] = r;
     }
 }
 
-__global__ void fill_quads_kernel(const int32_t* bins, int n_bins, const int32_t* n_quads, Quad* quads) {
+// strand_mask: the strands this launch sweeps (1: pass A, 2: pass B, 3: the single launch of the dump)
+__global__ void fill_quads_kernel(const int32_t* bins, int n_bins, const int32_t* n_quads, Quad* quads,
+                                  const LadderDesc* ladders, int strand_mask) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= *n_quads) return;
     int lo = 0, hi = n_bins;   // largest b with first_quad[b] <= q (empty bins share their successor's offset)
@@ -1065,12 +1140,11 @@ __global__ void fill_quads_kernel(const int32_t* bins, int n_bins, const int32_t
     }
     const int32_t* e = bins + (size_t)lo * BIN_STRIDE;
     const int j = q - e[2];
-    const int cls[3] = {1, 3, 2};
     Quad qd;
     qd.ladder = lo / UNIT_BINS;
     qd.first = e[1] + 4 * j;
     qd.count = min(4, e[0] - 4 * j);
-    qd.strands = cls[(lo / SW_LEVELS) % 3];
+    qd.strands = strand_mask & (ladders[qd.ladder].n_strands >= 2 ? 3 : 1);
     quads[q] = qd;
 }
 
@@ -1147,17 +1221,20 @@ __global__ void tally_kernel(const uint8_t* tag, const int16_t* h, const int32_t
 
 }  // namespace
 
-hipError_t launch_build_quads(const SwArgs& a, uint8_t* read_class, int32_t* perm, Quad* quads, int32_t* n_quads,
-                              int32_t* unit_cnt, int32_t* bins, int n_ladders, int64_t max_quads, hipStream_t s) {
+hipError_t launch_build_quads(const SwArgs& a, int pass, int rows_per_lane, uint8_t* read_key, int32_t* read_cnt, int32_t* perm,
+                              Quad* quads, int32_t* n_quads, int32_t* unit_cnt, int32_t* bins, int n_ladders, int64_t max_quads,
+                              hipStream_t s) {
     hipError_t e = hipMemsetAsync(n_quads, 0, sizeof(int32_t), s);
     if (e != hipSuccess) return e;
     if (a.n_units <= 0) return hipSuccess;
     const int n_bins = UNIT_BINS * n_ladders;
     if ((e = hipMemsetAsync(bins, 0, sw_bin_bytes(n_ladders), s)) != hipSuccess) return e;
-    read_class_kernel<<<a.n_units, 64, 0, s>>>(a, read_class, unit_cnt, bins);
+    if (pass == 0) read_class_kernel<<<a.n_units, 64, 0, s>>>(a, read_key, read_cnt, unit_cnt, bins);
+    else repack_kernel<<<a.n_units, 64, 0, s>>>(a, read_key, read_cnt, unit_cnt, bins, rows_per_lane >= 5 && 2 * rows_per_lane + 10 <= 32);
     bin_scan_kernel<<<1, 1024, 0, s>>>(bins, n_bins, n_quads);
-    scatter_kernel<<<a.n_units, 64, 0, s>>>(a, read_class, unit_cnt, bins, perm);
-    fill_quads_kernel<<<(unsigned)((max_quads + 255) / 256), 256, 0, s>>>(bins, n_bins, n_quads, quads);
+    scatter_kernel<<<a.n_units, 64, 0, s>>>(a, read_key, unit_cnt, bins, perm);
+    const int strand_mask = a.out_dump != nullptr ? 3 : 1 << pass;
+    fill_quads_kernel<<<(unsigned)((max_quads + 255) / 256), 256, 0, s>>>(bins, n_bins, n_quads, quads, a.ladders, strand_mask);
     return hipGetLastError();
 }
 

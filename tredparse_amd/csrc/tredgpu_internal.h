@@ -50,7 +50,8 @@ struct SwArgs {
     int32_t n_ladders;       // registered ladders (unit_ladder values outside [0, n_ladders) are clamped on the device)
     int32_t max_rows;        // 16 * rows-per-lane of the instantiation that will run
     tredgpu_sw_params p;
-    unsigned long long* stats;  // [SW_STAT_SLOTS][8], slot = workgroup & (SW_STAT_SLOTS - 1): work counters: trunk cols, continuation-pass cols, templates combined/dropped/emitted-from-trunk, waves
+    unsigned long long* stats;  // [SW_STAT_SLOTS][8], slot = workgroup & (SW_STAT_SLOTS - 1): work counters: trunk cols, continuation-pass cols, templates combined/dropped/emitted-from-trunk, waves, read-columns, reads handed to pass B
+    int32_t* best;              // per read: the arg-max word of sw_cont_kernel, carried from the strand-0 launch to the strand-1 launch
 };
 
 // per-wave counter updates are spread over this many 64-byte lines: half a million waves adding to one line
@@ -58,11 +59,15 @@ struct SwArgs {
 constexpr int SW_STAT_SLOTS = 1024;
 
 // sw_ladder.hip
-hipError_t launch_build_quads(const SwArgs& a, uint8_t* read_class, int32_t* perm, Quad* quads, int32_t* n_quads,
-                              int32_t* unit_cnt, int32_t* bins, int n_ladders, int64_t max_quads, hipStream_t s);
+// The SW kernel sweeps the strands in two launches (the per-template dump in one).  pass 0: classes, 6-mer counts
+// (read_cnt) and the quads of strand 0; pass 1, after pass 0's launch_sw_ladder: the quads of strand 1 from the reads
+// still open.  The two passes use the same workspaces one after the other.  read_key, read_cnt: one entry per read.
+hipError_t launch_build_quads(const SwArgs& a, int pass, int rows_per_lane, uint8_t* read_key, int32_t* read_cnt, int32_t* perm,
+                              Quad* quads, int32_t* n_quads, int32_t* unit_cnt, int32_t* bins, int n_ladders, int64_t max_quads,
+                              hipStream_t s);
 size_t sw_bin_bytes(int n_ladders);
 size_t sw_unit_cnt_bytes(int n_units);
-int64_t sw_max_quads(int64_t n_reads, int n_ladders);   // one partial quad per (ladder, class, level) bin
+int64_t sw_max_quads(int64_t n_reads, int n_ladders);   // of one pass: one partial quad per (ladder, level) bin
 // generic: some ladder's branch could reach the score filter on its own (the production kernel skips that sweep)
 hipError_t launch_sw_ladder(const SwArgs& a, int rows_per_lane, bool generic, int64_t max_quads, hipStream_t s);
 hipError_t launch_tally(const uint8_t* tag, const int16_t* h, int64_t n_reads,
