@@ -245,9 +245,9 @@ def test_feeder_with_the_selection_on_the_device_gives_the_plain_scans(cohort, m
         for _ in chunks:
             chunk, futs = feeder.next()
             scans = [f.result() for f in futs]
-            picks, parts = t.genotype_scans(engine, chunk, scans)
-            got += list(zip(chunk, scans))
-            assert sorted(parts) == [si for si, s in enumerate(scans) if s.opened]
+            samples = t.genotype_scans(engine, chunk, scans)
+            got += [(s.arg, s.scan) for s in samples]
+            assert [si for si, s in enumerate(samples) if s.pieces] == [si for si, s in enumerate(samples) if s.scan.opened]
     finally:
         feeder.close()
         ex.shutdown()
@@ -413,7 +413,7 @@ def test_run_many_with_the_selection_on_the_device_stops_when_the_consumer_fails
     class FailingEmit(object):
         error, n = None, 0
 
-        def submit(self, arg, scan, parts):
+        def submit(self, sample):
             self.n += 1
             if self.n == 1:
                 self.error = fail()

@@ -52,7 +52,7 @@ def compare(a, s, pieces, engine):
         bad.append("sequences")
     if not (np.array_equal(s.name_off, h.name_off) and s.name_blob == h.name_blob):
         bad.append("names")
-    ks = [k for k in range(len(h.names)) if k not in h.dropped]          # (a locus the reference would lose is in no batch)
+    ks = h.live_loci()                                                  # (a locus the reference would lose is in no batch)
     if not ks:
         return bad + ([] if not pieces else ["units"]), 0, 0
     hb = engine.genotype_packed(PackedUnits.from_scans([(h, ks)], maxinsert=o["maxinsert"], fullsearch=o["fullsearch"], clip=o["clip"]))
@@ -98,8 +98,7 @@ def device_scans(args, engine, batch):
         for _ in chunks:
             chunk, futs = feeder.next()
             scans = [f.result() for f in futs]
-            picks, parts = t.genotype_scans(engine, chunk, scans)
-            out += [(a, s, parts.get(si, [])) for si, (a, s) in enumerate(zip(chunk, scans))]
+            out += [(s.arg, s.scan, s.pieces) for s in t.genotype_scans(engine, chunk, scans)]
     finally:
         feeder.close()
         ex.shutdown()

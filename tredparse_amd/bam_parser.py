@@ -69,6 +69,10 @@ class SampleScan(object):
         u = self.unit[k]
         return int(u["read_first"]), int(u["read_first"]) + int(u["n_reads"])
 
+    def live_loci(self):
+        """The locus indices that go to the GPU: all but the dropped ones (admit), none of a file that did not open."""
+        return [k for k in range(len(self.names)) if k not in self.dropped] if self.opened else []
+
     def sequence(self, i):
         """Read i as the string the BAM record decodes to.  The whole 4-bit pool is decoded once, on first use
         (every record starts on a byte, so read i is text[2 * seq4_off[i] :][:read_len[i]])."""

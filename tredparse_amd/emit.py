@@ -8,7 +8,7 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 from datetime import date
 
-from .runtime import _options, timing_add
+from .runtime import timing_add
 
 logger = logging.getLogger("tredparse_amd.tred")
 
@@ -18,7 +18,7 @@ NATIVE_EMIT = True        # (tools/prof_host.py and the tests switch the native 
 class Emitter(object):
     """Writes the samples' <key>.json and <key>.tred.vcf.gz straight from a batch's result arrays and the scans' pools,
     natively (libtredbam.so tredbam_emit_sample_files, include/tredbam.h) on `workers` threads that run WITHOUT the
-    interpreter lock -- instead of building every sample's tredCalls dict (format_scans) and printing it (to_json,
+    interpreter lock -- instead of building every sample's tredCalls dict (format_sample) and printing it (to_json,
     to_vcf) in Python, which was what bounded a driver process.  The text is byte for byte the Python path's
     (tests/test_emit_native.py).  A sample the native printers do not cover -- --log DEBUG, --alignments, --consensus, --spectrum, a BAM that did not open, a
     batch the retries cut into single units, names outside ASCII -- goes through the Python path on the same thread.
@@ -48,56 +48,53 @@ class Emitter(object):
             self.tables[key] = bamio.emit_locus_table(self.repo, names) if ok else None
         return self.tables[key]
 
-    def submit(self, arg, scan, pieces):
-        """One sample of a genotyped batch (pieces: genotype_scans' parts for it)."""
+    def submit(self, sample):
+        """One sample of a genotyped batch (a runtime.Sample of tred.genotype_scans)."""
         self.room.acquire()
         try:
-            self.pool.submit(self._run, arg, scan, pieces)
+            self.pool.submit(self._run, sample)
         except BaseException:
             self.room.release()
             raise
 
-    def _run(self, arg, scan, pieces):
+    def _run(self, sample):
         t0 = time.perf_counter()
         try:
             if self.error is None:
-                self._emit(arg, scan, pieces)
+                self._emit(sample)
         except BaseException as e:
             self.error = e
         finally:
             self.room.release()
             timing_add(write=time.perf_counter() - t0)
 
-    def _python_path(self, arg, scan, pieces):
-        """The sample through format_scans and the Python writers (what the native path must equal)."""
-        from .tred import REPORT_TABLE, format_scans, unit_results, write_vcf_json
-        picks = [(0, scan, [k for _, _, ks in pieces for k in ks])]
-        res = unit_results({0: pieces})
-        result = format_scans([arg], [scan], picks, res, lazy_details=True)[0]
+    def _python_path(self, sample):
+        """The sample through format_sample and the Python writers (what the native path must equal)."""
+        from .tred import REPORT_TABLE, format_sample, write_vcf_json
+        scan, units = sample.scan, sample.units()
+        result = format_sample(sample, units, lazy_details=True)
         if not self.no_output:
             write_vcf_json(result, self.ref, self.repo, self.treds, quiet=not self.echo)
-            o = _options(arg)
-            per_locus = {k: r for (_, k), r in res.items()}
-            for name in o["reports"]:
+            for name in sample.o["reports"]:
                 suffix, _, text = REPORT_TABLE[name]
                 with open(result["samplekey"] + suffix, "w") as fp:
-                    fp.write(text(scan, result["tredCalls"], per_locus, o))
+                    fp.write(text(scan, result["tredCalls"], units, sample.o))
         if self.on_sample is not None:
             calls = result["tredCalls"]
             self.on_sample({"samplekey": result["samplekey"], "names": scan.names,
                             "printed": [n + ".1" in calls for n in scan.names],
                             "first_allele": [calls.get(n + ".1", -1) for n in scan.names]})
 
-    def _emit(self, arg, scan, pieces):
+    def _emit(self, sample):
         import ctypes as C
         import numpy as np
         from . import bamio
-        o = _options(arg)
-        native = scan.opened and len(pieces) == 1 and o["log"] != "DEBUG" and not o["reports"] and pieces[0][0].joint_units is not None
+        o, scan, pieces = sample.o, sample.scan, sample.pieces
+        native = scan.opened and len(pieces) == 1 and o["log"] != "DEBUG" and not o["reports"] and pieces[0].result.joint_units is not None
         table = self._table(scan.names) if native else None
         if table is None or (self.no_output and self.on_sample is None):
             if not (self.no_output and self.on_sample is None and o["log"] != "DEBUG"):
-                self._python_path(arg, scan, pieces)
+                self._python_path(sample)
             else:                # nothing to print: the loci the grid refused are still reported, as the Python path does
                 from .models import STATUS_ERRORS
                 for br, i0, ks in pieces:
@@ -136,7 +133,7 @@ class Emitter(object):
         rc = self.lib.tredbam_emit_sample_files(C.addressof(table), len(scan.names), C.addressof(eb), C.addressof(es), C.addressof(eo),
                                                 status.ctypes.data, text, cap, C.byref(got))
         if rc == 1:
-            return self._python_path(arg, scan, pieces)
+            return self._python_path(sample)
         if rc < 0:
             why = self.lib.tredbam_emit_last_error().decode("utf-8", "replace") or str(rc)
             print("Error writing: {} ({})".format(o["samplekey"], why), file=sys.stderr)

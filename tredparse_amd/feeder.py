@@ -137,7 +137,7 @@ def _select_plan(o, f, loci, sites, regions, readlen, sexed, p):
     import numpy as np
     from ._lib import SELECT_TASK_DTYPE
     from .bam_parser import MAX_READ_LEN, ladder_fits, selection_range, y_regions
-    if o["log"] == "DEBUG" or o["reports"] or not (o["repeatpairs"] or o["clip"]):
+    if o["log"] == "DEBUG" or o["reports"] or not o["count_repeatpairs"]:
         return None
     if len(sites) == 0 or (sites["tid"] < 0).any() or (p.tasks["n_chunks"] < 0).any() or readlen > MAX_READ_LEN:
         return None

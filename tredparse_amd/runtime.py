@@ -1,9 +1,10 @@
 """What the pieces of a driver process share (tred.py the CLI and run_many, feeder.py the GPU-inflate pipeline, emit.py
-the native writer): the stage timers and the named form of run()'s argument tuple."""
+the native writer): the stage timers, the named form of run()'s argument tuple and the record of one genotyped sample."""
 import json
 import os
 import threading
 import time
+from collections import namedtuple
 
 from .bam_parser import scan_sample
 
@@ -51,14 +52,47 @@ _TAIL = ("alignments", "consensus", "consensus_partial", "spectrum")        # me
 
 def _options(arg):
     """The reference's run() argument tuple, named.  Members 10-13, where the tuple has them (option_tail), are --alignments,
-    --consensus, --consensus-partial and --spectrum; `reports`: the REPORTS among them that are on, in that order."""
+    --consensus, --consensus-partial and --spectrum; `reports`: the REPORTS among them that are on, in that order;
+    `count_repeatpairs`: what the kernels, the tally and the device's selection go by -- `repeatpairs`, or --useclippedreads."""
     samplekey, bam, repo, names, maxinsert, fullsearch, clip, alts, repeatpairs, log = arg[:10]
     o = dict(samplekey=samplekey, bam=bam, repo=repo, names=list(names), maxinsert=maxinsert,
              fullsearch=fullsearch, clip=clip, alts=alts, repeatpairs=repeatpairs, log=log)
     for at, name in enumerate(_TAIL, 10):
         o[name] = bool(arg[at]) if len(arg) > at else False
     o["reports"] = [name for name in REPORTS if o[name]]
+    o["count_repeatpairs"] = bool(repeatpairs or clip)
     return o
+
+
+# what the samples of one GPU batch must share: the kernel-side options and the reports computed with the batch
+BatchKey = namedtuple("BatchKey", "maxinsert fullsearch clip count_repeatpairs debug reports consensus_partial")
+
+
+def batch_key(o):
+    return BatchKey(o["maxinsert"], o["fullsearch"], o["clip"], o["count_repeatpairs"], o["log"] == "DEBUG", tuple(o["reports"]),
+                    o["consensus_partial"])
+
+
+# the units of one sample in one BatchResult: `result`, the sample's first unit in it, the locus indices of its units there
+Piece = namedtuple("Piece", "result first loci")
+
+
+class Sample(object):
+    """One sample between its scan and its files (tred.genotype_scans fills it, tred.format_sample and the Emitter read it):
+    arg, the run() argument tuple; o, _options(arg); scan, the SampleScan that was genotyped (the host's after a fall-back from the
+    device's selection); loci, scan.live_loci(); pieces, [Piece] -- one unless the retries cut the batch into single units."""
+    __slots__ = ("arg", "o", "scan", "loci", "pieces")
+
+    def __init__(self, arg, scan):
+        self.arg, self.o = arg, _options(arg)
+        self.take(scan)
+
+    def take(self, scan):                  # (the sample's scan from here on: what was genotyped from an earlier one is forgotten)
+        self.scan, self.loci, self.pieces = scan, scan.live_loci(), []
+
+    def units(self):
+        """{locus index: UnitResult} of the genotyped units."""
+        return {k: p.result.unit(p.first + j) for p in self.pieces for j, k in enumerate(p.loci)}
 
 
 def option_tail(alignments=False, consensus=False, consensus_partial=False, spectrum=False):

@@ -37,7 +37,8 @@ from .models import GridError, SparseDist, format_call, pair_summaries
 
 logging.basicConfig()
 logger = logging.getLogger(__name__)
-from .runtime import TIMING, _options, collect_sample, mark, option_tail, timeline_dump, timing_add                    # noqa: F401  (shared with feeder.py / emit.py)
+from .runtime import (TIMING, Piece, Sample, _options, batch_key, collect_sample, mark, option_tail,      # noqa: F401  (shared
+                      timeline_dump, timing_add)                                                        # with feeder.py / emit.py)
 from .feeder import (_InflateFeeder, _plan_sample, _scan_planned, pinned_bytes,                # noqa: F401
                      release_inflaters)
 from .emit import Emitter                                                                  # noqa: F401
@@ -270,20 +271,18 @@ def debug_lines(scan, k, res):
                              _py2_str(((m1 + m2) + m3) + m4)]))
 
 
-def _genotype(engine, picks, o):
-    """PackedUnits of `picks` through the GPU.  A batch that fails as a whole is retried sample by sample and then
-    unit by unit, so that one unit the kernels reject costs only itself (the reference loses only the failing
-    locus too).  Returns {scan index: [(BatchResult, first unit of the sample in it, its locus indices)]} -- one piece
-    per sample unless the retries went down to single units."""
+def _genotype(engine, samples):
+    """The live loci of the samples of one option group (the first one's options are all's) packed on the host and sent through the
+    GPU.  A batch that fails as a whole is retried sample by sample and then unit by unit, so that one unit the kernels reject costs
+    only itself (the reference loses only the failing locus too).  A call that succeeds adds a Piece to each of its samples."""
     from ._lib import TredGpuError
     from .engine import PackedUnits
-    kw = dict(maxinsert=o["maxinsert"], fullsearch=o["fullsearch"], clip=o["clip"],
-              repeatpairs=o["repeatpairs"] or o["clip"])
-    out = {}
+    o = samples[0].o
+    kw = dict(maxinsert=o["maxinsert"], fullsearch=o["fullsearch"], clip=o["clip"], repeatpairs=o["count_repeatpairs"])
 
-    def attempt(sub):
+    def attempt(sub):                     # sub: [(Sample, the loci of it in this call)]
         t0 = time.perf_counter()
-        batch = PackedUnits.from_scans([(s, ks) for _, s, ks in sub], **kw)
+        batch = PackedUnits.from_scans([(s.scan, ks) for s, ks in sub], **kw)
         timing_add(pack=time.perf_counter() - t0)
         if batch.n_units == 0:
             return
@@ -294,25 +293,24 @@ def _genotype(engine, picks, o):
             for name in o["reports"]:
                 setattr(br, name, REPORT_TABLE[name][1](engine, batch, br, winners, o))
         i = 0
-        for si, _, ks in sub:
+        for s, ks in sub:
             if ks:
-                out.setdefault(si, []).append((br, i, list(ks)))
+                s.pieces.append(Piece(br, i, list(ks)))
             i += len(ks)
 
     try:
-        attempt(picks)
+        attempt([(s, s.loci) for s in samples])
     except TredGpuError as e:
         logger.error("GPU batch failed (%s); retrying in smaller pieces", e)
-        for si, s, ks in picks:
+        for s in samples:
             try:
-                attempt([(si, s, ks)])
+                attempt([(s, s.loci)])
             except TredGpuError:
-                for k in ks:
+                for k in s.loci:
                     try:
-                        attempt([(si, s, [k])])
+                        attempt([(s, [k])])
                     except TredGpuError as e1:
-                        logger.error("Exception on `%s` %s (%s)", s.path, s.names[k], e1)
-    return out
+                        logger.error("Exception on `%s` %s (%s)", s.scan.path, s.scan.names[k], e1)
 
 
 def _called_alleles(br):
@@ -321,39 +319,39 @@ def _called_alleles(br):
     return [sorted({int(c["h1"]) // int(p), int(c["h2"]) // int(p)}) if int(c["status"]) == 0 else [] for c, p in zip(calls, period)]
 
 
-def _called(scan, calls, res):
-    """(k, name, UnitResult) of every locus that was called and has a result (res: {locus index: UnitResult})."""
+def _called(scan, calls, units):
+    """(k, name, UnitResult) of every locus that was called and has a result (units: Sample.units())."""
     for k, name in enumerate(scan.names):
-        r = res.get(k)
+        r = units.get(k)
         if r is not None and name + ".details" in calls:
             yield k, name, r
 
 
-def consensus_text(scan, calls, res, o):
+def consensus_text(scan, calls, units, o):
     """--consensus: {locus: {"alleles": [AlleleConsensus.to_dict(), ...]}} for every called locus, one entry per distinct
-    called allele of at least one unit, smaller first; sorted keys.  res: {locus index: UnitResult with .consensus}.
+    called allele of at least one unit, smaller first; sorted keys.  units: {locus index: UnitResult with .consensus}.
     --consensus-partial: every allele with its `partial`, `ambiguous` and `beyond` counts."""
     out = {}
-    for _, name, r in _called(scan, calls, res):
+    for _, name, r in _called(scan, calls, units):
         alleles = sorted(set(int(a) for a in (calls[name + ".1"], calls[name + ".2"]) if int(a) >= 1))
         out[name] = {"alleles": [r.consensus[a].to_dict(partial=o["consensus_partial"]) for a in alleles]}
     return json.dumps(out, sort_keys=True, indent=1) + "\n"
 
 
-def spectrum_text(scan, calls, res, o):
-    """--spectrum: {locus: RepeatSpectrum.to_dict()} for every called locus; sorted keys.  res: {locus index: UnitResult
+def spectrum_text(scan, calls, units, o):
+    """--spectrum: {locus: RepeatSpectrum.to_dict()} for every called locus; sorted keys.  units: {locus index: UnitResult
     with .spectrum}."""
-    return json.dumps({name: r.spectrum.to_dict() for _, name, r in _called(scan, calls, res)}, sort_keys=True, indent=1) + "\n"
+    return json.dumps({name: r.spectrum.to_dict() for _, name, r in _called(scan, calls, units)}, sort_keys=True, indent=1) + "\n"
 
 
-def alignments_text(scan, calls, res, o):
+def alignments_text(scan, calls, units, o):
     """--alignments: for every `details` entry of every called locus, in `details` order, a header line
     `>{locus} {tag} h={h} {+|-} {read id}` (- : the template's reverse complement), the reference's verbose block for the
-    pair (bam_parser.py:145-147) and a blank line.  res: {locus index: UnitResult with .alignments}."""
+    pair (bam_parser.py:145-147) and a blank line.  units: {locus index: UnitResult with .alignments}."""
     from ._lib import TAG_NAMES
     out = []
-    for k, name, r in _called(scan, calls, res):
-        _, details, _ = tally(scan, k, r.tags, r.hs, repeatpairs=o["repeatpairs"] or o["clip"], lazy=True)
+    for k, name, r in _called(scan, calls, units):
+        _, details, _ = tally(scan, k, r.tags, r.hs, repeatpairs=o["count_repeatpairs"], lazy=True)
         a, _ = scan.reads_of(k)
         for i, t, h in zip(details.reads.tolist(), details.tags.tolist(), details.hs.tolist()):
             x = r.alignments[i - a]
@@ -363,7 +361,7 @@ def alignments_text(scan, calls, res, o):
 
 
 # report (runtime.REPORTS) -> (what follows <samplekey> in its file's name; compute(engine, batch, BatchResult, winners, o): the
-# BatchResult's member of that name; text(scan, calls, res, o): the file).  _genotype and Emitter._python_path loop over it.
+# BatchResult's member of that name; text(scan, calls, Sample.units(), o): the file).  _genotype and Emitter._python_path loop over it.
 REPORT_TABLE = {
     "alignments": (".alignments.txt", lambda e, b, br, w, o: e.alignments(b, winners=w), alignments_text),
     "consensus": (".consensus.json", lambda e, b, br, w, o: e.consensus(b, _called_alleles(br), winners=w,
@@ -373,107 +371,82 @@ REPORT_TABLE = {
 
 
 def genotype_scans(engine, task_args, scans):
-    """GPU half of a batch: the kernels' results for every unit of the scans, (picks, parts) with parts as _genotype
-    returns them (unit_results turns them into per-unit views).
+    """GPU half of a batch: a Sample per task, in task order, with the kernels' results for its units in its pieces.
     The kernel-side options of a GPU batch are the batch's: tasks that differ in them go in separate batches (the CLI's
-    are uniform; API callers of run_many may mix them)."""
+    are uniform; API callers of run_many may mix them).  `scans` is only read: after a fall-back to the host, Sample.scan is the host's."""
     from ._lib import TredGpuError
-    picks = [(si, s, [k for k in range(len(s.names)) if k not in s.dropped] if s.opened else [])
-             for si, s in enumerate(scans)]
+    samples = [Sample(arg, scan) for arg, scan in zip(task_args, scans)]
     t0 = time.perf_counter()
     # the leases on the inflaters that hold device-selected reads (feeder.DeviceChunk), taken down before on_the_host
     # replaces scans: they are given back in ONE place, the finally below, whatever became of their samples
     leases = set(s.device.chunk for s in scans if getattr(s, "device", None) is not None)
     groups = {}
-    for pick, arg in zip(picks, task_args):
-        o = _options(arg)
+    for s in samples:
         # (a scan whose reads the device selected and still holds -- feeder._device_scan -- goes to the call that packs them there)
-        on_device = getattr(pick[1], "device", None) is not None
-        key = (o["maxinsert"], o["fullsearch"], o["clip"], o["repeatpairs"] or o["clip"], o["log"] == "DEBUG", tuple(o["reports"]), o["consensus_partial"], on_device)
-        groups.setdefault(key, (o, []))[1].append(pick)
-    parts = {}
+        groups.setdefault((batch_key(s.o), getattr(s.scan, "device", None) is not None), []).append(s)
 
-    def on_the_host(o, sub):
-        """The samples of `sub` scanned by the host after all and genotyped the host-packed way (scans[] is the caller's list:
-        the writers find the host's scan there)."""
-        again = []
-        for si, s, _ in sub:
-            h = collect_sample(task_args[si], getattr(engine, "long_reads", False))
-            scans[si] = h
-            picks[si] = (si, h, [k for k in range(len(h.names)) if k not in h.dropped] if h.opened else [])
-            again.append(picks[si])
-        parts.update(_genotype(engine, again, o))
+    def on_the_host(sub):                  # the samples of `sub` scanned by the host after all and genotyped the host-packed way
+        for s in sub:
+            s.take(collect_sample(s.arg, getattr(engine, "long_reads", False)))
+        _genotype(engine, sub)
     try:
-        for key, (o, sub) in groups.items():
-            if not key[-1]:
-                parts.update(_genotype(engine, sub, o))
+        for (_, on_device), sub in groups.items():
+            if not on_device:
+                _genotype(engine, sub)
                 continue
             try:
-                parts.update(_genotype_selected(engine, sub, o))
+                _genotype_selected(engine, sub)
             except TredGpuError as e:
                 # the call over the device-held reads failed as a whole: those samples are scanned on the host after all and
                 # go the host-packed way, whose retries cost a bad unit only itself
                 logger.error("GPU batch over device-selected reads failed (%s); scanning its %d samples on the host", e, len(sub))
-                on_the_host(o, sub)
+                on_the_host(sub)
                 continue
             # A selected record without a sequence (SEQ '*': pysam gives None and the reference's len(seq) raises,
             # bam_parser.py:129-133) drops its locus in the host's scan (TREDBAM_UNIT_NO_SEQ); the device's selection does not
             # look for it, but the lengths it brings back show it: such a sample is the host's.
-            odd = [p for p in sub if len(p[1].read_len) and int(p[1].read_len.min()) == 0]
+            odd = [s for s in sub if len(s.scan.read_len) and int(s.scan.read_len.min()) == 0]
             if odd:
-                on_the_host(o, odd)
+                on_the_host(odd)
     finally:
         for lease in leases:                   # the inflaters that held the device's selections are the feeder's again
             lease.done()
     timing_add(gpu=time.perf_counter() - t0, gpu_calls=len(groups))
-    return picks, parts
+    return samples
 
 
-def _genotype_selected(engine, picks, o):
+def _genotype_selected(engine, samples):
     """_genotype for scans whose reads are on the device: one engine.genotype_selected call for all of them."""
     t0 = time.perf_counter()
-    scans = [s for _, s, _ in picks]
-    br = engine.genotype_selected(scans, maxinsert=o["maxinsert"], fullsearch=o["fullsearch"], clip=o["clip"])
+    o = samples[0].o
+    br = engine.genotype_selected([s.scan for s in samples], maxinsert=o["maxinsert"], fullsearch=o["fullsearch"], clip=o["clip"])
     br.repeatpairs = True
     timing_add(pack=time.perf_counter() - t0)
-    out, i = {}, 0
-    for si, s, ks in picks:
-        out[si] = [(br, i, list(ks))]
-        i += len(s.names)
-    return out
+    i = 0
+    for s in samples:
+        s.pieces = [Piece(br, i, list(s.loci))]
+        i += len(s.scan.names)
 
 
-def unit_results(parts, only=None):
-    """{(scan index, k): UnitResult} of genotype_scans' parts (only: that scan index alone)."""
-    res = {}
-    for si, pieces in parts.items():
-        if only is not None and si != only:
-            continue
-        for br, i0, ks in pieces:
-            for j, k in enumerate(ks):
-                res[(si, k)] = br.unit(i0 + j)
-    return res
+def format_sample(sample, units, lazy_details=False):
+    """One sample's result dict from the kernels' results (units: sample.units())."""
+    o, scan = sample.o, sample.scan
+    result = _skeleton(o, scan)
+    pairs = pair_summaries(scan) if sample.loci else None
+    for k in (k for k in sample.loci if k in units):
+        if o["log"] == "DEBUG":
+            debug_lines(scan, k, units[k])
+        try:
+            _fill_unit(result["tredCalls"], scan, k, units[k], o["count_repeatpairs"], pairs, lazy=lazy_details)
+        except GridError as e:
+            logger.error("Exception on `%s` %s (%s)", o["bam"], scan.names[k], e)
+    return result
 
 
-def format_scans(task_args, scans, picks, res, lazy_details=False):
-    """Host half of a batch: the result dicts in task order from the kernels' results."""
+def format_scans(samples, lazy_details=False):
+    """Host half of a batch: the result dicts of genotype_scans' samples, in their order."""
     t1 = time.perf_counter()
-    results = []
-    for si, (arg, scan) in enumerate(zip(task_args, scans)):
-        o = _options(arg)
-        result = _skeleton(o, scan)
-        pairs = pair_summaries(scan) if picks[si][2] else None
-        for k in picks[si][2]:
-            if (si, k) not in res:
-                continue
-            if o["log"] == "DEBUG":
-                debug_lines(scan, k, res[(si, k)])
-            try:
-                _fill_unit(result["tredCalls"], scan, k, res[(si, k)], o["repeatpairs"] or o["clip"], pairs,
-                           lazy=lazy_details)
-            except GridError as e:
-                logger.error("Exception on `%s` %s (%s)", o["bam"], scan.names[k], e)
-        results.append(result)
+    results = [format_sample(s, s.units(), lazy_details) for s in samples]
     timing_add(format=time.perf_counter() - t1)
     return results
 
@@ -482,10 +455,7 @@ def finish_batch(engine, task_args, scans, lazy_details=False):
     """GPU half + formatting for the scans of one batch; returns the result dicts in task order.  lazy_details:
     `<locus>.details` as bam_parser.Details views (list-like) and the sparse distributions as models.SparseDist
     (dict-like) instead of lists and dicts; to_json prints both natively."""
-    if not task_args:
-        return []
-    picks, parts = genotype_scans(engine, task_args, scans)
-    return format_scans(task_args, scans, picks, unit_results(parts), lazy_details=lazy_details)
+    return format_scans(genotype_scans(engine, task_args, scans), lazy_details=lazy_details) if task_args else []
 
 
 def run(arg, engine=None):
@@ -648,11 +618,12 @@ def run_many(task_args, engine, pool=None, batch=64, sink=None, threads=1, lazy_
         for chunk, scans in scanned():
             if emit is not None:
                 mark("scanned", n=len(chunk))
-                picks, parts = genotype_scans(engine, chunk, scans)
+                samples = genotype_scans(engine, chunk, scans)
                 mark("genotyped", n=len(chunk))
                 t0 = time.perf_counter()
-                for si, (arg, scan) in enumerate(zip(chunk, scans)):
-                    emit.submit(arg, scan, parts.get(si, []))
+                for sample in samples:
+                    emit.submit(sample)
+                del sample          # (left bound, it alone would keep the chunk's BatchResult until the next chunk's loop: freed in ITS `format`)
                 timing_add(format=time.perf_counter() - t0)
                 mark("submitted", n=len(chunk))
                 if emit.error is not None:        # a writer thread failed: stop scanning and genotyping the rest of the cohort
