@@ -14,6 +14,7 @@
 
 #include "tredgpu_internal.h"
 #include "inflater_internal.h"
+#include "kmer_host.h"
 
 using namespace tredgpu;
 
@@ -509,30 +510,19 @@ int tredgpu_set_ladders(tredgpu_ctx* c, int32_t n, const char* const* prefix, co
         d.n_strands = 2;
         // 6-mer presence bitmaps over ALL templates of each strand (exact strand filter in the kernel).  A template
         // N scores 0 against every base: it neither breaks nor feeds a run of matches, so a window with N
-        // positions stands for all its fillings (the bound's run-length argument then holds unchanged).
+        // positions stands for all its fillings (the bound's run-length argument then holds unchanged) -- and for a
+        // ladder with an N the class table says how many N columns a window costs at least (kmer_host.h).
         d.kmer_ok = 1;
         for (int s = 0; s < 2; ++s) {
-            std::vector<uint32_t> bits(128, 0u);
-            for (int u = 1; u <= mu; ++u) {
-                std::vector<int8_t> t(*A[s]);
-                for (int k = 0; k < u; ++k) t.insert(t.end(), Rep[s]->begin(), Rep[s]->end());
-                t.insert(t.end(), B[s]->begin(), B[s]->end());
-                for (size_t i = 0; i + 6 <= t.size(); ++i) {
-                    uint32_t code = 0;
-                    int wild[6], nw = 0;
-                    for (int k = 0; k < 6; ++k) {
-                        if (t[i + k] > 3) wild[nw++] = k;
-                        else code |= (uint32_t)(t[i + k] & 3) << (2 * k);
-                    }
-                    for (uint32_t f = 0; f < (1u << (2 * nw)); ++f) {
-                        uint32_t cf = code;
-                        for (int j = 0; j < nw; ++j) cf |= ((f >> (2 * j)) & 3u) << (2 * wild[j]);
-                        bits[cf >> 5] |= 1u << (cf & 31);
-                    }
-                }
-            }
+            std::vector<uint32_t> bits, cls;
+            const bool with_n = kmer_host::build_tables(*A[s], *Rep[s], *B[s], mu, bits, cls);
             d.kmer_off[s] = (int)seq.size();
             seq.insert(seq.end(), bits.begin(), bits.end());
+            d.kmer_n = with_n ? 1 : 0;   // (the strands hold the same letters: the same answer twice)
+            if (with_n) {
+                d.kcls_off[s] = (int)seq.size();
+                seq.insert(seq.end(), cls.begin(), cls.end());
+            }
         }
         max_u = std::max(max_u, mu);
     }
@@ -636,6 +626,7 @@ static int run_sw_device(tredgpu_ctx* c, const uint32_t* packed, const int64_t* 
     if ((rc = ensure(c, c->ws_best, (size_t)n_reads * sizeof(int32_t)))) return rc;
     if ((rc = ensure(c, c->ws_cnt, (size_t)n_reads * sizeof(int32_t)))) return rc;
     a.best = (int32_t*)c->ws_best.p;
+    a.read_cnt = (const int32_t*)c->ws_cnt.p;
     if (c->ws_stats.p == nullptr) {
         if ((rc = ensure(c, c->ws_stats, SW_STAT_SLOTS * 8 * sizeof(unsigned long long)))) return rc;
         HIPCHK(c, hipMemsetAsync(c->ws_stats.p, 0, SW_STAT_SLOTS * 8 * sizeof(unsigned long long), c->stream));

@@ -37,6 +37,18 @@ constexpr int KONE = 1 << KSH;
 constexpr int PAYMASK = KONE - 1;
 constexpr int NEG = -(1 << 30);
 constexpr int PADNEG = -64 * KONE;
+constexpr int CNT_UNFILTERED = 0x7FFF;   // stored 6-mer weight of a read the filter does not apply to
+
+// The 6-mer weight of a read on a strand and the score cap it gives (sw_cont_kernel's strand filter has the argument
+// for a ladder without N, DESIGN.md 4.1 the whole proof).  cnt = the read's windows present in the strand's templates
+// (a window with a read N counts as present); jsum = over those windows the fewest template N positions a window needs to
+// produce them (0 for a window with a read N, and for every window of a ladder without N).  A run of matches through
+// k windows is l = k + 5 columns long, each window sits on a template window with at least j(w) N columns, and a column
+// lies in at most six windows: the run has at least ceil(sum j / 6) columns that score 0, so at most
+// k + 5 - ceil(sum j / 6) matches.  Runs use distinct windows and a break costs >= 5 matches (the filter's premise):
+//   score <= match * (5 + W),   W = cnt - ceil(jsum / 6).
+__device__ __forceinline__ int kmer_weight(int cnt, int jsum) { return cnt - (jsum + 5) / 6; }
+__device__ __forceinline__ int kmer_cap(int w, int match) { return (w + 5) * match; }
 
 template <int CTRL>
 __device__ __forceinline__ int dpp_row_shr(int old, int x) {
@@ -577,45 +589,23 @@ __global__ __launch_bounds__(64, W) void sw_cont_kernel(SwArgs a) {
         // 6-mers are exact; no template of this strand can reach the score filter (>= 30,
         // bam_parser.py:134) unless that many read 6-mers occur somewhere in the strand's templates.
         // Read windows containing N count as present; a template N scores 0 against every base, so template
-        // windows with N stand for all their fillings (tredgpu_set_ladders).  Skipped for the dump (all positive
-        // scores wanted) and for scorings outside the bound's premise.
+        // windows with N stand for all their fillings (tredgpu_set_ladders) -- and every N column under a window is a
+        // match the alignment does not get (kmer_weight).  Skipped for the dump (all positive scores wanted) and for
+        // scorings outside the bound's premise.
         int kcap = 1 << 20;  // per read: upper bound of any score on this strand
-        // (a 6-mer window starting in this lane ends at most 5 bases into the next lane's rows: needs R >= 5;
-        //  with fewer rows per lane the per-read classes of read_class_kernel already removed hopeless strands)
+        // (the cap is used by the 112- and 160-row instantiations, as it was when the kernel counted the windows itself
+        //  -- a window starting in a lane's rows had to end within the next lane's; in the others the per-read classes
+        //  of read_class_kernel already removed hopeless strands)
         if constexpr (R >= 5 && 2 * R + 10 <= 32) if (!full_dump && kmer_thr > 0 && __builtin_amdgcn_readfirstlane(ld->kmer_ok) != 0) {
-            const uint32_t* bm = a.seqw + __builtin_amdgcn_readfirstlane(ld->kmer_off[s]);
-            // this lane's rows as 2-bit codes / N-or-padding flags, loaded here, per strand: they and the window
-            // indices below depend on the read only, and hoisted out of the strand loop they would sit in 2R + 2
-            // registers across the column loop -- i.e. in scratch
-            uint32_t pk_s, nk_s;
-            {
-                int L_s = L, row0_s = row0;
-                asm volatile("" : "+v"(L_s), "+v"(row0_s));
-                uint64_t code2;
-                uint32_t nmask;
-                load_rows<R>(a, read_base(), L_s, row0_s, code2, nmask);
-                const int n_real = min(max(L_s - row0_s, 0), R);                 // rows of this lane inside the read
-                pk_s = (uint32_t)code2 & ((1u << (2 * R)) - 1u);                             // (codes of N / padding rows are never
-                nk_s = (nmask | ~((1u << n_real) - 1u)) & ((1u << R) - 1u);        //  looked at: their windows count as present)
-            }
-            const uint32_t pk_n = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pk_s, 0x101, 0xF, 0xF, false);        // row_shl:1
-            const uint32_t nk_n = (uint32_t)__builtin_amdgcn_update_dpp(0x3FF, (int)nk_s, 0x101, 0xF, 0xF, false);
-            const uint32_t comb = pk_s | ((pk_n & 0x3FFu) << (2 * R));
-            const uint32_t ncomb = nk_s | ((nk_n & 0x1Fu) << R);
-            int cnt = 0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const uint32_t win = (comb >> (2 * r)) & 0xFFFu;
-                const bool has_n = ((ncomb >> r) & 0x3Fu) != 0;
-                const bool in_read = row0 + r + 5 < L;
-                const uint32_t word = bm[win >> 5];
-                cnt += in_read && (has_n || ((word >> (win & 31)) & 1u));
-            }
-            cnt += dpp_row_shr<0x111>(0, cnt);
-            cnt += dpp_row_shr<0x112>(0, cnt);
-            cnt += dpp_row_shr<0x114>(0, cnt);
-            cnt += dpp_row_shr<0x118>(0, cnt);
-            kcap = (cnt + 5) * a.p.match;  // lane 15 of each read holds the read's total
+            // The read's 6-mer weight on this strand, as read_class_kernel stored it (the count of its windows present
+            // in the strand's templates, less what the template N columns under them take away: kmer_weight) -- the
+            // number repack_kernel tests, so the re-pack's entry test is this one.  (Counting here again took about
+            // ten dependent loads and 70 VALU instructions per wave and strand.)  CNT_UNFILTERED: an over-long read,
+            // which L = 0 closes below.
+            // (the strand's half of the word W0 | W1 << 16)
+            const int jb = lane_now() >> 4;
+            const int cnt = jb < q_count ? (int)reinterpret_cast<const uint16_t*>(a.read_cnt)[2 * (int64_t)a.perm[q_first + jb] + s] : 0;
+            if (cnt != CNT_UNFILTERED) kcap = kmer_cap(cnt, a.p.match);
             if (__builtin_amdgcn_ballot_w64(valid && jl == 15 && cnt >= kmer_thr) == 0) continue;
         }
         // Strand exit.  No alignment scores more than cap; a template only matters if it passes its score filter
@@ -934,7 +924,6 @@ constexpr int BIN_STRIDE = 16;   // ints: every bin counter on its own 64-byte l
 constexpr int SW_LEVELS = 32;
 constexpr int UNIT_BINS = SW_LEVELS;   // bins one unit can feed in one pass
 constexpr int KEY_NONE = 0xFF;
-constexpr int CNT_UNFILTERED = 0x7FFF;   // stored 6-mer count of a read the filter does not apply to
 __device__ __forceinline__ int level_key(int cnt) { return SW_LEVELS - 1 - min(SW_LEVELS - 1, cnt / 6); }
 __device__ __forceinline__ int kmer_threshold(const tredgpu_sw_params& p) {
     // 6-mer filter premise: every run break costs >= 5 matches (see sw_cont_kernel)
@@ -959,14 +948,27 @@ __device__ __forceinline__ void claim_bin_runs(const int* hist, int lad, int g, 
 // are applied to the masks once per word -- ~7 VALU instructions per base where the base-by-base loop (shift register,
 // run length since the last N, two compares) took ~25: 0.35 -> 0.25 ms per 30 000 units (staging the records in LDS
 // and 64-bit entries holding both strands' words were tried on top: no gain).
-__device__ __forceinline__ void kmer_counts(const uint32_t* rec, int L, const uint32_t* bm, int& cnt0, int& cnt1) {
+// NCLS (a ladder with an N in its templates): kc = the two strands' class tables (2 x 512 words of 4-bit entries, LDS);
+// the results are the weights cnt - ceil(jsum / 6) (kmer_weight), jsum = the classes of the counted windows without a
+// read N (an absent window's class is 0 in the table).  Two more LDS lookups per base, for those ladders only.
+template <bool NCLS>
+__device__ __forceinline__ void kmer_counts(const uint32_t* rec, int L, const uint32_t* bm, const uint32_t* kc, int& cnt0, int& cnt1) {
     const int nb = (L + 15) >> 4;
     uint32_t prev = 0, mprev = 0;
     cnt0 = cnt1 = 0;
+    int j0 = 0, j1 = 0;
     for (int wi = 0; wi < nb; ++wi) {
         const uint32_t w = rec[wi];
         const uint32_t m = (rec[nb + (wi >> 1)] >> ((wi & 1) * 16)) & 0xffffu;
         uint32_t b0 = 0, b1 = 0;
+        // N flags of bases -5 .. 15 of this word at bits 0 .. 20; window j holds an N when one of bits j .. j+5 is set
+        const uint32_t mm = m << 5 | mprev >> 11;
+        const uint32_t hn = mm | mm >> 1 | mm >> 2 | mm >> 3 | mm >> 4 | mm >> 5;
+        // counted: read positions 5 .. L-1
+        const int left = L - wi * 16;
+        uint32_t cm = left >= 16 ? 0xffffu : (1u << left) - 1u;
+        if (wi == 0) cm &= ~0x1fu;
+        const uint32_t plain = cm & ~hn;   // counted windows without an N: the ones that have a class
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             // bases j-5 .. j of this word, base j-5 in the low bits: the 6-mer's index is the low 12 bits of t (bitmap
@@ -975,23 +977,27 @@ __device__ __forceinline__ void kmer_counts(const uint32_t* rec, int L, const ui
             const uint32_t at = __builtin_amdgcn_ubfe(t, 5, 7);
             b0 = (__builtin_amdgcn_ubfe(bm[at], t, 1) << j) | b0;
             b1 = (__builtin_amdgcn_ubfe(bm[128 + at], t, 1) << j) | b1;
+            if (NCLS) {
+                const uint32_t at4 = __builtin_amdgcn_ubfe(t, 3, 9), sh = (t & 7u) << 2;
+                const bool use = (plain >> j) & 1u;
+                j0 += use ? (int)__builtin_amdgcn_ubfe(kc[at4], sh, 4) : 0;
+                j1 += use ? (int)__builtin_amdgcn_ubfe(kc[512 + at4], sh, 4) : 0;
+            }
         }
-        // N flags of bases -5 .. 15 of this word at bits 0 .. 20; window j holds an N when one of bits j .. j+5 is set
-        const uint32_t mm = m << 5 | mprev >> 11;
-        const uint32_t hn = mm | mm >> 1 | mm >> 2 | mm >> 3 | mm >> 4 | mm >> 5;
-        // counted: read positions 5 .. L-1
-        const int left = L - wi * 16;
-        uint32_t cm = left >= 16 ? 0xffffu : (1u << left) - 1u;
-        if (wi == 0) cm &= ~0x1fu;
         cnt0 += __builtin_popcount((b0 | hn) & cm);
         cnt1 += __builtin_popcount((b1 | hn) & cm);
         prev = w;
         mprev = m;
     }
+    if (NCLS) {
+        cnt0 = kmer_weight(cnt0, j0);
+        cnt1 = kmer_weight(cnt1, j1);
+    }
 }
 
-// read_cnt[rd] = cnt0 | cnt1 << 16: the read's 6-mer counts on the two strands (CNT_UNFILTERED where the filter does not
-// apply), kept for repack_kernel.  A read outside pass A gets tag NONE here; pass B overwrites it if the read gets there.
+// read_cnt[rd] = W0 | W1 << 16: the read's 6-mer weights on the two strands (the plain counts for a ladder without N;
+// CNT_UNFILTERED where the filter does not apply), kept for repack_kernel and for sw_cont_kernel's score cap.  A read
+// outside pass A gets tag NONE here; pass B overwrites it if the read gets there.
 __global__ __launch_bounds__(64) void read_class_kernel(SwArgs a, uint8_t* read_key, int32_t* read_cnt, int32_t* unit_cnt,
                                                           int32_t* bin_total) {
     const int g = blockIdx.x;
@@ -1006,9 +1012,14 @@ __global__ __launch_bounds__(64) void read_class_kernel(SwArgs a, uint8_t* read_
     // the two 4096-bit presence maps of the ladder, in LDS: every base of every read looks both up, and a
     // lookup in global memory (even an L1 hit) stalled the loop for its whole latency
     __shared__ uint32_t bm[2][128];
+    __shared__ uint32_t kc[2][512];   // the N classes of the 6-mers, for a ladder whose templates hold an N
     __shared__ int hist[UNIT_BINS];
+    const bool ncls = filt && ld->kmer_n != 0;   // (per ladder: the same for the whole workgroup)
     if (filt) {
         for (int k = threadIdx.x; k < 256; k += (int)blockDim.x) bm[k >> 7][k & 127] = a.seqw[ld->kmer_off[k >> 7] + (k & 127)];
+    }
+    if (ncls) {
+        for (int k = threadIdx.x; k < 1024; k += (int)blockDim.x) kc[k >> 9][k & 511] = a.seqw[ld->kcls_off[k >> 9] + (k & 511)];
     }
     for (int k = threadIdx.x; k < UNIT_BINS; k += (int)blockDim.x) hist[k] = 0;
     __syncthreads();
@@ -1016,7 +1027,10 @@ __global__ __launch_bounds__(64) void read_class_kernel(SwArgs a, uint8_t* read_
         int cnt0 = CNT_UNFILTERED, cnt1 = CNT_UNFILTERED;
         const int L = a.read_len[rd];
         // over-long reads go to the SW kernel, which flags them (in pass A: unfiltered reads have bit 0)
-        if (filt && L <= a.max_rows) kmer_counts(a.packed + a.read_off[rd], L, &bm[0][0], cnt0, cnt1);
+        if (filt && L <= a.max_rows) {
+            if (ncls) kmer_counts<true>(a.packed + a.read_off[rd], L, &bm[0][0], &kc[0][0], cnt0, cnt1);
+            else kmer_counts<false>(a.packed + a.read_off[rd], L, &bm[0][0], nullptr, cnt0, cnt1);
+        }
         read_cnt[rd] = cnt0 | cnt1 << 16;
         a.best[rd] = -1;
         if (cnt0 >= thr) {
@@ -1039,7 +1053,7 @@ __global__ __launch_bounds__(64) void read_class_kernel(SwArgs a, uint8_t* read_
 // Pass B's reads: class bit 1 (the stored count against the threshold) and the entry test sw_cont_kernel makes for
 // strand 1 -- the same cap, the same still_open(first template) with the arg-max pass A left.  Never stricter than the
 // kernel's, which keeps its tests: a read that gets here is handled as in a single launch.  kcap_in_kernel: the
-// instantiation that will run derives a score cap from the 6-mer count (5 <= R <= 11).
+// instantiation that will run derives a score cap from the 6-mer weight (5 <= R <= 11).
 __global__ __launch_bounds__(64) void repack_kernel(SwArgs a, uint8_t* read_key, const int32_t* read_cnt, int32_t* unit_cnt,
                                                       int32_t* bin_total, int kcap_in_kernel) {
     const int g = blockIdx.x;
@@ -1060,7 +1074,7 @@ __global__ __launch_bounds__(64) void repack_kernel(SwArgs a, uint8_t* read_key,
         const int L = a.read_len[rd];
         const int cnt1 = (int)((uint32_t)read_cnt[rd] >> 16);
         const bool counted = cnt1 != CNT_UNFILTERED;
-        const int kcap = with_kcap && counted ? (cnt1 + 5) * a.p.match : 1 << 20;
+        const int kcap = with_kcap && counted ? kmer_cap(cnt1, a.p.match) : 1 << 20;
         const int cap = min(kcap, L * a.p.match);
         const int min_score = max(min(L, first_T) >> 1, 30);
         const bool open = max(min_score, (a.best[rd] >> 12) + 1) <= cap;

@@ -20,6 +20,8 @@ struct LadderDesc {
     int32_t n_strands;
     int32_t kmer_ok;       // 1: kmer_off[] bitmaps usable (max_units > 0)
     int32_t kmer_off[2];   // WORD offsets of the 4096-bit 6-mer presence bitmaps (128 words) per strand
+    int32_t kmer_n;        // 1: some template holds an N -- kcls_off[] tables present (kmer_host.h)
+    int32_t kcls_off[2];   // WORD offsets of the 6-mer N classes (4 bits per 6-mer, 512 words) per strand
 };
 
 // A quad = up to four reads of one ladder (any units) that share a wavefront (16 lanes each).
@@ -52,6 +54,7 @@ struct SwArgs {
     tredgpu_sw_params p;
     unsigned long long* stats;  // [SW_STAT_SLOTS][8], slot = workgroup & (SW_STAT_SLOTS - 1): work counters: trunk cols, continuation-pass cols, templates combined/dropped/emitted-from-trunk, waves, read-columns, reads handed to pass B
     int32_t* best;              // per read: the arg-max word of sw_cont_kernel, carried from the strand-0 launch to the strand-1 launch
+    const int32_t* read_cnt;    // per read: the 6-mer weights W0 | W1 << 16 of read_class_kernel (the score cap of a strand)
 };
 
 // per-wave counter updates are spread over this many 64-byte lines: half a million waves adding to one line
