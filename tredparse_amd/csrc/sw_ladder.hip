@@ -38,6 +38,11 @@ constexpr int PAYMASK = KONE - 1;
 constexpr int NEG = -(1 << 30);
 constexpr int PADNEG = -64 * KONE;
 constexpr int CNT_UNFILTERED = 0x7FFF;   // stored 6-mer weight of a read the filter does not apply to
+// The bounded-gain test of steady_exit (sw_cont_kernel); -DSW_EXIT_BOUND=0 compiles it out (the Makefile builds that
+// kernel into libtredgpu_noexit.so, and tests/test_sw_exit_gpu.py compares the columns swept by the two libraries).
+#ifndef SW_EXIT_BOUND
+#define SW_EXIT_BOUND 1
+#endif
 
 // The 6-mer weight of a read on a strand and the score cap it gives (sw_cont_kernel's strand filter has the argument
 // for a ladder without N, DESIGN.md 4.1 the whole proof).  cnt = the read's windows present in the strand's templates
@@ -824,12 +829,50 @@ __global__ __launch_bounds__(64, W) void sw_cont_kernel(SwArgs a) {
         // column one period before it (same letters, same recurrence).  Every later template end then has the score of
         // this one (the trunk's best does not move, the continuation vectors do not depend on u); the score a template
         // needs never decreases with u; so after a template end that was DROPPED in that state all later ones would be
-        // dropped too: the strand is done.  (Typically 5-6 periods after a read's peak: that long a horizontal gap out
-        // of the best alignment still beats an alignment that starts afresh inside the repeat.)  Tested only after
+        // dropped too: the strand is done.  (Some periods after a read's peak -- about 2.4 more than the bounded-gain test
+        // below needs, by the CPU model of tests/sw_exit_model.py: a horizontal gap out of the best alignment keeps beating
+        // an alignment that starts afresh inside the repeat for that long.)  Tested only after
         // dropped template ends -- reads before their peak keep improving -- and never for the dump.
         int ok_run = 0;
         auto steady_exit = [&](const uint32_t ends_before) -> bool {
             if (full_dump || ((cnt_ends ^ ends_before) & 0xFF00u) == 0) { ok_run = 0; return false; }
+#if SW_EXIT_BOUND
+            // (in the two production instantiations of reads up to 160 bp, 7 and 10 rows per lane: in the others, and in the
+            //  GENERIC variants, the compiler answered the added block with another register allocation of the column blocks
+            //  -- the build's static census gave the 16-row trunk column 497 -> 513 issue cycles; what that costs at 250 bp
+            //  was never timed)
+            // (and only once some read of the wave has a candidate: the ends dropped before that are the first templates,
+            //  too short to pass the score filter -- the test cannot hold there, and it is not free)
+            if constexpr (!GENERIC && (R == 7 || R == 10)) if (__builtin_amdgcn_ballot_w64(best >= 0) != 0) {
+                // Bounded-gain exit (DESIGN.md 4.1 has the proof).  Template u - 1 was dropped for every read at column c.
+                // If every H and E entry of column c either records a start column >= alen + period, or scores so little
+                // that score + G(row) < need(u) -- G(row) = match * (L - 1 - row) bounds what any path can still gain in the
+                // read rows below `row` -- then no later template reaches the score it needs: an alignment that starts at
+                // alen + period or later is, moved one period to the left, an alignment of the template before it (dropped,
+                // by induction; need never decreases); one that ends by column c is an alignment of template u - 1; one that
+                // crosses column c does so in some entry, whose recorded prefix either starts late (swap it in: the first
+                // case) or is bounded by the second test.  One boundary is enough; the two-boundary test below stays for
+                // the reads whose old entries are still within reach.
+                // In the kernel's scale an entry of row i holds (score + (i + c) * ge) << 18 | start (E: column c + 1), so
+                // the entry minus thr(row) = (need - G(row) + (i + c) * ge) << 18 keeps the start bits and is negative exactly
+                // when the second test holds: masked to sign | start column, an unsigned minimum skips those entries.
+                const int c = next_end - period;
+                // (the lane's first row from the lane index, taken on the spot: with row0 the compiler computes the lane-
+                //  invariant parts of the thresholds at the kernel's entry and keeps them through the column loop)
+                const int r0 = (lane_now() & 15) * R;
+                const int bestS = best >> 12, bestU = 511 - ((best >> 3) & 511);
+                const int need = max(max(min(L, alen + period * u + blen) >> 1, 30), u >= bestU ? bestS + 1 : bestS);
+                int nt = (L - 1 - r0) * mK - need * KONE - (r0 + c) * geK;   // -thr(first row of the lane)
+                uint32_t lo = 0x3FFFFu;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    lo = min(lo, min((uint32_t)(H[r] + nt) & 0x8003FE00u, (uint32_t)(E[r] + nt - geK) & 0x8003FE00u));
+                    nt -= mK + geK;
+                    asm volatile("" : "+v"(nt), "+v"(lo));   // (row by row: computed ahead, the thresholds of all rows are live at once)
+                }
+                if (__builtin_amdgcn_ballot_w64(lo < ((uint32_t)(alen + period) << 9)) == 0) return true;
+            }
+#endif
             const uint32_t thr = (uint32_t)(alen + (ok_run ? period : 0)) << 9;
             uint32_t lo = 0x3FFFFu;
 #pragma unroll
