@@ -41,7 +41,9 @@ struct tredgpu_ctx {
     Buf d_model;
     bool have_model = false;
     // workspaces (grow-only, reused across calls)
-    Buf ws_quads, ws_counter, ws_drop, ws_grid, ws_stats, ws_perm, ws_class, ws_gdesc, ws_gtile, ws_gctr, ws_ucnt, ws_bins, ws_kde, ws_best, ws_cnt;
+    Buf ws_quads, ws_counter, ws_drop, ws_stats, ws_perm, ws_class, ws_ucnt, ws_bins, ws_best, ws_cnt;
+    // the likelihood grid's: what plan_grid (grid_host.h) sizes, and the two ints of query_max_insert
+    struct GridBufs { Buf pool, descs, items, counters, kde, unit_max; } grid;
     int* h_pin = nullptr;  // pinned word for small read-backs
     hipEvent_t sync_ev = nullptr;  // stream_sync's event
     size_t grid_pool_bytes = GRID_POOL_BYTES;   // TREDGPU_GRID_POOL_MB overrides (tuning / tests of the multi-pass path)
@@ -392,7 +394,8 @@ void tredgpu_destroy(tredgpu_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)stream_sync(c);
     for (Buf* b : {&c->d_ladders, &c->d_seq, &c->d_model, &c->ws_quads, &c->ws_counter, &c->ws_drop,
-                   &c->ws_grid, &c->ws_stats, &c->ws_perm, &c->ws_class, &c->ws_gdesc, &c->ws_gtile, &c->ws_gctr, &c->ws_ucnt, &c->ws_bins, &c->ws_kde, &c->ws_best, &c->ws_cnt})
+                   &c->ws_stats, &c->ws_perm, &c->ws_class, &c->ws_ucnt, &c->ws_bins, &c->ws_best, &c->ws_cnt, &c->grid.pool, &c->grid.descs,
+                   &c->grid.items, &c->grid.counters, &c->grid.kde, &c->grid.unit_max})
         release(*b);
     for (Buf& b : c->st) release(b);
     for (auto& t : c->timers)
@@ -753,9 +756,9 @@ static int check_grid_common(tredgpu_ctx* c, const tredgpu_unit_params* units, i
 // One 4-byte read-back; the fused path asks before it launches the SW kernel, so the stream is idle.
 static int query_max_insert(tredgpu_ctx* c, const tredgpu_unit_params* units, int32_t n_units, int out[2]) {
     int rc;
-    if ((rc = ensure(c, c->ws_counter, 64))) return rc;
+    if ((rc = ensure(c, c->grid.unit_max, 2 * sizeof(int)))) return rc;
     if (!c->h_pin) HIPCHK(c, hipHostMalloc((void**)&c->h_pin, 64, hipHostMallocDefault));
-    int* d = (int32_t*)c->ws_counter.p + 12;
+    int* d = (int*)c->grid.unit_max.p;
     HIPCHK(c, launch_unit_max(units, n_units, d, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->h_pin, d, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_sync(c));
@@ -764,80 +767,45 @@ static int query_max_insert(tredgpu_ctx* c, const tredgpu_unit_params* units, in
     return 0;
 }
 
-static int run_grid_device(tredgpu_ctx* c, const tredgpu_unit_params* units, int32_t n_units, int32_t hist_stride,
-                           const int32_t* full_cnt, const int32_t* pref_cnt, const int32_t* rept_cnt,
-                           const int32_t* global_lens, const int32_t* target_lens, tredgpu_call* calls,
-                           const int64_t* grid_off, double* grid_dump, double* marg, int32_t marg_stride,
-                           const int* limits /* {max maxinsert, max n_target}; NULL: ask the device */,
-                           const int64_t* joint_off = nullptr, double* joint = nullptr, int32_t* joint_n = nullptr,
-                           double* joint_total = nullptr) {
-    if (n_units == 0) return 0;
+// The grid passes over arrays in DEVICE memory.  io: the caller's side of the arguments (units, histograms, pair lengths,
+// calls and the optional outputs; everything else zero) -- the workspace's side is filled in here.
+static int run_grid_device(tredgpu_ctx* c, GridArgs a, const int* limits /* {max maxinsert, max n_target}; NULL: ask the device */) {
+    if (a.n_units == 0) return 0;
     int rc;
     int lim[2];
     if (limits) { lim[0] = limits[0]; lim[1] = limits[1]; }
-    else if ((rc = query_max_insert(c, units, n_units, lim))) return rc;
-    const int max_insert = lim[0], max_target = lim[1];
-    // every axis is a subset of {distinct sizes} U {max_partial} plus at most maxinsert arithmetic entries
-    const int cap = std::min(std::max(hist_stride + 1 + std::max(max_insert, 0), 8), GRID_MAX_ROWS);
-    const size_t slot_max = grid_slot_doubles_max(cap, cap, max_target) * sizeof(double);
-    // the pool: everything the batch can ask for if that is small, else GRID_POOL_BYTES and as many passes
-    // as it takes (units that find their sub-pool full are deferred to the next pass).  The kernels use it as up to 16
-    // sub-pools, unit g in sub-pool g % n: "everything" = the worst case of the fullest residue class, n times
-    const size_t slot_room = slot_max + 16 * sizeof(double);
-    const size_t all_bytes = 16 * grid_units_per_subpool(n_units, 16) * slot_room;
-    const size_t pool_bytes = std::max(std::min(all_bytes, c->grid_pool_bytes), slot_room);
-    const bool may_defer = all_bytes > pool_bytes;
-    const size_t item_cap = grid_item_slots(n_units, cap, cap);
-    if ((rc = ensure(c, c->ws_grid, pool_bytes))) return rc;
-    if ((rc = ensure(c, c->ws_gdesc, (size_t)n_units * grid_desc_bytes()))) return rc;
-    if ((rc = ensure(c, c->ws_gtile, item_cap * grid_item_bytes() + 64))) return rc;
-    if ((rc = ensure(c, c->ws_gctr, grid_counter_bytes()))) return rc;
-    // the units' paired-end KDEs (grid_kde_kernel -> grid_prepare_kernel): 1000 doubles + an outcome per unit
-    const size_t kde_pdf_bytes = (size_t)n_units * TREDGPU_SPAN * sizeof(double);
-    if ((rc = ensure(c, c->ws_kde, kde_pdf_bytes + (size_t)n_units * sizeof(int32_t)))) return rc;
+    else if ((rc = query_max_insert(c, a.units, a.n_units, lim))) return rc;
+    GridWorkspace w;
+    const GridPlan& p = w.plan = plan_grid(a.n_units, a.hist_stride, lim[0], lim[1], c->grid_pool_bytes);
+    if ((rc = ensure(c, c->grid.pool, p.pool_bytes))) return rc;
+    if ((rc = ensure(c, c->grid.descs, p.desc_bytes))) return rc;
+    if ((rc = ensure(c, c->grid.items, p.items_bytes))) return rc;
+    if ((rc = ensure(c, c->grid.counters, p.counter_bytes))) return rc;
+    if ((rc = ensure(c, c->grid.kde, p.kde_bytes))) return rc;
     if (!c->h_pin) HIPCHK(c, hipHostMalloc((void**)&c->h_pin, 64, hipHostMallocDefault));
-    GridArgs a;
-    a.units = units;
-    a.n_units = n_units;
-    a.hist_stride = hist_stride;
-    a.full_cnt = full_cnt;
-    a.pref_cnt = pref_cnt;
-    a.rept_cnt = rept_cnt;
-    a.global_lens = global_lens;
-    a.target_lens = target_lens;
-    a.calls = calls;
-    a.grid_off = grid_off;
-    a.grid_dump = grid_dump;
-    a.marg = marg;
-    a.marg_stride = marg_stride;
+    w.descs = (GridDescs*)c->grid.descs.p;
+    w.pool = (double*)c->grid.pool.p;
+    w.items = (GridItems*)c->grid.items.p;
+    w.counters = (GridCounterBlock*)c->grid.counters.p;
+    w.kde_pdf = (double*)c->grid.kde.p;
+    w.kde_rc = (int32_t*)((char*)c->grid.kde.p + p.kde_pdf_bytes);
     a.model = (const ModelConst*)c->d_model.p;
-    a.joint_off = joint_off;
-    a.joint = joint;
-    a.joint_n = joint_n;
-    a.joint_total = joint_total;
-    a.kde_pdf = nullptr;
-    a.kde_status = nullptr;
-    a.unit_pdf = (double*)c->ws_kde.p;
-    a.unit_kde_rc = (int32_t*)((char*)c->ws_kde.p + kde_pdf_bytes);
-    a.max_target = max_target;
-    {
-        ScopedTimer tm(c, TREDGPU_KERNEL_GRID);
-        for (int pass = 0;; ++pass) {
-            // KDE (first pass only) / prepare / pairs / reduce, each bracketed by its own events
-            static const int PHASE[4][2] = {{8, TREDGPU_KERNEL_GRID_KDE}, {1, TREDGPU_KERNEL_GRID_PREPARE},
-                                            {2, TREDGPU_KERNEL_GRID_PAIRS}, {4, TREDGPU_KERNEL_GRID_REDUCE}};
-            for (int ph = pass == 0 ? 0 : 1; ph < 4; ++ph) {
-                ScopedTimer phase_tm(c, PHASE[ph][1]);
-                HIPCHK(c, launch_grid_pass(a, pass, c->ws_gdesc.p, (double*)c->ws_grid.p, pool_bytes / sizeof(double), cap,
-                                           cap, c->ws_gtile.p, item_cap, c->ws_gctr.p, c->stream, PHASE[ph][0]));
-            }
-            if (!may_defer) break;
-            HIPCHK(c, hipMemcpyAsync(c->h_pin, (const char*)c->ws_gctr.p + grid_deferred_offset(), sizeof(int),
-                                     hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, stream_sync(c));
-            if (c->h_pin[0] == 0) break;
-            if (pass >= 1000) return fail(c, -10, "likelihood grid: scratch pool passes do not converge");
+    a.unit_pdf = w.kde_pdf;
+    a.unit_kde_rc = w.kde_rc;
+    a.max_target = p.max_target;
+    ScopedTimer tm(c, TREDGPU_KERNEL_GRID);
+    for (int pass = 0;; ++pass) {
+        // KDE (first pass only) / prepare / pairs / reduce, each bracketed by its own events
+        for (GridPhase ph : {GridPhase::KDE, GridPhase::PREPARE, GridPhase::PAIRS, GridPhase::REDUCE}) {
+            if (ph == GridPhase::KDE && pass > 0) continue;
+            ScopedTimer phase_tm(c, (int)ph);
+            HIPCHK(c, launch_grid_phase(a, w, pass, ph, c->stream));
         }
+        if (!p.may_defer) break;
+        HIPCHK(c, hipMemcpyAsync(c->h_pin, grid_deferred(w), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, stream_sync(c));
+        if (c->h_pin[0] == 0) break;
+        if (pass >= 1000) return fail(c, -10, "likelihood grid: scratch pool passes do not converge");
     }
     return 0;
 }
@@ -857,31 +825,32 @@ static int likelihood_grid_impl(tredgpu_ctx* c, int mem, const tredgpu_unit_para
     if (joint_off && (!joint || !joint_n || !joint_total)) return fail(c, -2, "joint_off, joint, joint_n and joint_total go together");
     if (marg && marg_stride <= 0) return fail(c, -2, "marg_stride must be > 0");
     HIPCHK(c, hipSetDevice(c->device));
-    if (mem == TREDGPU_MEM_DEVICE)
-        return run_grid_device(c, units, n_units, hist_stride, full_cnt, pref_cnt, rept_cnt, global_lens, target_lens,
-                               calls, grid_off, grid_dump, marg, marg_stride, nullptr, joint_off, joint, joint_n,
-                               joint_total);
+    GridArgs a = {};
+    a.n_units = n_units; a.hist_stride = hist_stride; a.marg_stride = marg_stride;
+    if (mem == TREDGPU_MEM_DEVICE) {
+        a.units = units; a.full_cnt = full_cnt; a.pref_cnt = pref_cnt; a.rept_cnt = rept_cnt;
+        a.global_lens = global_lens; a.target_lens = target_lens; a.calls = calls;
+        a.grid_off = grid_off; a.grid_dump = grid_dump; a.marg = marg;
+        a.joint_off = joint_off; a.joint = joint; a.joint_n = joint_n; a.joint_total = joint_total;
+        return run_grid_device(c, a, nullptr);
+    }
     if (mem != TREDGPU_MEM_HOST) return fail(c, -2, "bad mem");
     if (n_units == 0) return 0;
     int limits[2] = {0, 0};
     for (int g = 0; g < n_units; ++g)
         if ((rc = check_unit(c, g, units[g], nullptr, hist_stride, n_global_total, n_target_total, marg ? marg_stride : 0, limits))) return rc;
-    const tredgpu_unit_params* d_units; const int32_t *d_f, *d_p, *d_r, *d_gl, *d_tl;
-    const int64_t* d_goff = nullptr; tredgpu_call* d_calls; double* d_dump = nullptr; double* d_marg = nullptr;
-    const int64_t* d_joff = nullptr; double* d_joint = nullptr; int32_t* d_jn = nullptr; double* d_jt = nullptr;
     const size_t g = (size_t)n_units, hn = g * hist_stride;
     const std::vector<Staged> list = {
-        arr_in(d_units, units, g), arr_in(d_f, full_cnt, hn), arr_in(d_p, pref_cnt, hn), arr_in(d_r, rept_cnt, hn),
-        arr_in(d_gl, global_lens, (size_t)n_global_total), arr_in(d_tl, target_lens, (size_t)n_target_total),   // (always: 16 bytes when empty)
-        arr_out(d_calls, calls, g),
-        grid_off ? arr_in(d_goff, grid_off, g + 1) : absent, grid_off ? arr_out(d_dump, grid_dump, (size_t)grid_off[n_units] * 6) : absent,
-        marg ? arr_out(d_marg, marg, g * 2 * marg_stride) : absent,
-        joint_off ? arr_in(d_joff, joint_off, g + 1) : absent, joint_off ? arr_out(d_joint, joint, (size_t)joint_off[n_units] * 3) : absent,
-        joint_off ? arr_out(d_jn, joint_n, g) : absent, joint_off ? arr_out(d_jt, joint_total, g) : absent,
+        arr_in(a.units, units, g), arr_in(a.full_cnt, full_cnt, hn), arr_in(a.pref_cnt, pref_cnt, hn), arr_in(a.rept_cnt, rept_cnt, hn),
+        arr_in(a.global_lens, global_lens, (size_t)n_global_total), arr_in(a.target_lens, target_lens, (size_t)n_target_total),   // (always: 16 bytes when empty)
+        arr_out(a.calls, calls, g),
+        grid_off ? arr_in(a.grid_off, grid_off, g + 1) : absent, grid_off ? arr_out(a.grid_dump, grid_dump, (size_t)grid_off[n_units] * 6) : absent,
+        marg ? arr_out(a.marg, marg, g * 2 * marg_stride) : absent,
+        joint_off ? arr_in(a.joint_off, joint_off, g + 1) : absent, joint_off ? arr_out(a.joint, joint, (size_t)joint_off[n_units] * 3) : absent,
+        joint_off ? arr_out(a.joint_n, joint_n, g) : absent, joint_off ? arr_out(a.joint_total, joint_total, g) : absent,
     };
     rc = stage(c, list);
-    if (!rc) rc = run_grid_device(c, d_units, n_units, hist_stride, d_f, d_p, d_r, d_gl, d_tl, d_calls, d_goff, d_dump, d_marg,
-                                  marg_stride, limits, d_joff, d_joint, d_jn, d_jt);
+    if (!rc) rc = run_grid_device(c, a, limits);
     return finish(c, list, rc);
 }
 
@@ -945,24 +914,20 @@ int tredgpu_pe_kde(tredgpu_ctx* c, int mem, const tredgpu_unit_params* units, in
 // for and what the DEVICE branch of tredgpu_genotype_batch runs on the caller's arrays.  read_pair_id: ws_drop is the
 // caller's to size.
 static int run_fused_device(tredgpu_ctx* c, const uint32_t* packed, const int64_t* read_off, const int32_t* read_len, int64_t n_reads,
-                            const int32_t* unit_read_off, const int32_t* unit_ladder, const tredgpu_unit_params* units,
-                            int32_t n_units, const tredgpu_sw_params* params, int max_len, const int32_t* read_pair_id,
-                            const int32_t* global_lens, const int32_t* target_lens, uint8_t* out_tag, int16_t* out_h,
-                            int16_t* out_score, int32_t hist_stride, int32_t* full_cnt, int32_t* pref_cnt, int32_t* rept_cnt,
-                            tredgpu_call* calls, double* marg, int32_t marg_stride, const int* limits,
-                            const int64_t* joint_off = nullptr, double* joint = nullptr, int32_t* joint_n = nullptr,
-                            double* joint_total = nullptr) {
+                            const int32_t* unit_read_off, const int32_t* unit_ladder, const tredgpu_sw_params* params, int max_len,
+                            const int32_t* read_pair_id, uint8_t* out_tag, int16_t* out_h, int16_t* out_score, int32_t* full_cnt,
+                            int32_t* pref_cnt, int32_t* rept_cnt, GridArgs io /* but for the histograms */, const int* limits) {
     int rc;
-    if (n_reads > 0 && (rc = run_sw_device(c, packed, read_off, read_len, n_reads, unit_read_off, unit_ladder, n_units, params,
+    if (n_reads > 0 && (rc = run_sw_device(c, packed, read_off, read_len, n_reads, unit_read_off, unit_ladder, io.n_units, params,
                                            max_len, out_tag, out_h, out_score, nullptr, 0)))
         return rc;
     {
         ScopedTimer tm(c, TREDGPU_KERNEL_TALLY);
-        HIPCHK(c, launch_tally(out_tag, out_h, n_reads, unit_read_off, n_units, read_pair_id, hist_stride, full_cnt, pref_cnt,
+        HIPCHK(c, launch_tally(out_tag, out_h, n_reads, unit_read_off, io.n_units, read_pair_id, io.hist_stride, full_cnt, pref_cnt,
                                rept_cnt, (uint8_t*)c->ws_drop.p, c->stream));
     }
-    return run_grid_device(c, units, n_units, hist_stride, full_cnt, pref_cnt, rept_cnt, global_lens, target_lens, calls,
-                           nullptr, nullptr, marg, marg_stride, limits, joint_off, joint, joint_n, joint_total);
+    io.full_cnt = full_cnt; io.pref_cnt = pref_cnt; io.rept_cnt = rept_cnt;
+    return run_grid_device(c, io, limits);
 }
 
 // The whole path for a batch in HOST memory with everything the product's writers print, in ONE call with ONE wait:
@@ -997,9 +962,10 @@ int tredgpu_genotype_batch_joint(tredgpu_ctx* c, const uint32_t* packed, const i
     int max_len;
     if ((rc = host_max_len(c, params, read_len, n_reads, &max_len))) return rc;
     if (read_pair_id && (rc = ensure(c, c->ws_drop, (size_t)n_reads))) return rc;
-    const uint32_t* d_packed; const int64_t* d_off; const int32_t *d_len, *d_uoff, *d_ulad, *d_pid = nullptr, *d_gl, *d_tl;
-    const tredgpu_unit_params* d_units; const int64_t* d_joff;
-    uint8_t* d_tag; int16_t *d_h, *d_score; int32_t *d_f, *d_p, *d_r; tredgpu_call* d_calls; double *d_marg, *d_joint, *d_jt; int32_t* d_jn;
+    const uint32_t* d_packed; const int64_t* d_off; const int32_t *d_len, *d_uoff, *d_ulad, *d_pid = nullptr;
+    uint8_t* d_tag; int16_t *d_h, *d_score; int32_t *d_f, *d_p, *d_r;
+    GridArgs a = {};
+    a.n_units = n_units; a.hist_stride = hist_stride; a.marg_stride = marg_stride;
     const size_t n = (size_t)n_reads, g = (size_t)n_units, hn = g * hist_stride;
     const std::vector<Staged> list = {
         // (without reads the caller may pass neither packed nor read_off)
@@ -1008,14 +974,13 @@ int tredgpu_genotype_batch_joint(tredgpu_ctx* c, const uint32_t* packed, const i
         arr_out(d_tag, out_tag, n), arr_out(d_h, out_h, n), arr_out(d_score, out_score, n),
         read_pair_id ? arr_in(d_pid, read_pair_id, n) : absent,
         arr_scratch(d_f, hn), arr_scratch(d_p, hn), arr_out(d_r, rept_cnt, hn),       // (rept_cnt: copied back where the caller passed it)
-        arr_in(d_units, units, g), arr_in(d_gl, global_lens, (size_t)n_global_total), arr_in(d_tl, target_lens, (size_t)n_target_total),
-        arr_out(d_calls, calls, g), arr_out(d_marg, marg, g * 2 * marg_stride),
-        arr_in(d_joff, joint_off, g + 1), arr_out(d_joint, joint, (size_t)joint_off[n_units] * 3), arr_out(d_jn, joint_n, g), arr_out(d_jt, joint_total, g),
+        arr_in(a.units, units, g), arr_in(a.global_lens, global_lens, (size_t)n_global_total), arr_in(a.target_lens, target_lens, (size_t)n_target_total),
+        arr_out(a.calls, calls, g), arr_out(a.marg, marg, g * 2 * marg_stride),
+        arr_in(a.joint_off, joint_off, g + 1), arr_out(a.joint, joint, (size_t)joint_off[n_units] * 3), arr_out(a.joint_n, joint_n, g), arr_out(a.joint_total, joint_total, g),
     };
     rc = stage(c, list);
-    if (!rc) rc = run_fused_device(c, d_packed, d_off, d_len, n_reads, d_uoff, d_ulad, d_units, n_units, params, max_len, d_pid, d_gl,
-                                   d_tl, d_tag, d_h, d_score, hist_stride, d_f, d_p, d_r, d_calls, d_marg, marg_stride, limits,
-                                   d_joff, d_joint, d_jn, d_jt);
+    if (!rc) rc = run_fused_device(c, d_packed, d_off, d_len, n_reads, d_uoff, d_ulad, params, max_len, d_pid, d_tag, d_h, d_score, d_f, d_p, d_r,
+                                   a, limits);
     return finish(c, list, rc);
 }
 
@@ -1071,18 +1036,19 @@ int tredgpu_genotype_selected(tredgpu_ctx* c, const tredgpu_selected_units* segs
         if ((rc = check_unit(c, u, units[u], unit_ladder, hist_stride, n_global_total, n_target_total, marg_stride, limits))) return rc;
     const size_t n = (size_t)n_reads, offs = n ? n + 1 : 0, nu = (size_t)n_units, hn = nu * hist_stride;
     uint32_t* d_packed; int64_t* d_off; int32_t* d_len; uint8_t* d_seq4; int64_t* d_s4off; uint8_t* d_names; int64_t* d_nmoff;
-    const int32_t *d_uoff, *d_ulad, *d_task, *d_gl, *d_tl;
-    const int64_t *d_uw, *d_us, *d_un, *d_joff;
-    const tredgpu_unit_params* d_units;
-    uint8_t* d_tag; int16_t *d_h, *d_score; int32_t *d_f, *d_p, *d_r; tredgpu_call* d_calls; double *d_marg, *d_joint, *d_jt; int32_t* d_jn;
+    const int32_t *d_uoff, *d_ulad, *d_task;
+    const int64_t *d_uw, *d_us, *d_un;
+    uint8_t* d_tag; int16_t *d_h, *d_score; int32_t *d_f, *d_p, *d_r;
+    GridArgs a = {};
+    a.n_units = n_units; a.hist_stride = hist_stride; a.marg_stride = marg_stride;
     const std::vector<Staged> list = {
         arr_scratch(d_packed, (size_t)unit_word_off[n_units]), arr_scratch(d_off, n + 1), arr_out(d_len, read_len, n),
         arr_in(d_uoff, unit_read_off, nu + 1), arr_in(d_ulad, unit_ladder, nu),
         arr_out(d_tag, out_tag, n), arr_out(d_h, out_h, n), arr_out(d_score, out_score, n),
         arr_scratch(d_f, hn), arr_scratch(d_p, hn), arr_out(d_r, rept_cnt, hn),       // (rept_cnt: copied back where the caller passed it)
-        arr_in(d_units, units, nu), arr_in(d_gl, global_lens, (size_t)n_global_total), arr_in(d_tl, target_lens, (size_t)n_target_total),
-        arr_out(d_calls, calls, nu), arr_out(d_marg, marg, nu * 2 * marg_stride),
-        arr_in(d_joff, joint_off, nu + 1), arr_out(d_joint, joint, (size_t)joint_off[n_units] * 3), arr_out(d_jn, joint_n, nu), arr_out(d_jt, joint_total, nu),
+        arr_in(a.units, units, nu), arr_in(a.global_lens, global_lens, (size_t)n_global_total), arr_in(a.target_lens, target_lens, (size_t)n_target_total),
+        arr_out(a.calls, calls, nu), arr_out(a.marg, marg, nu * 2 * marg_stride),
+        arr_in(a.joint_off, joint_off, nu + 1), arr_out(a.joint, joint, (size_t)joint_off[n_units] * 3), arr_out(a.joint_n, joint_n, nu), arr_out(a.joint_total, joint_total, nu),
         arr_in(d_task, (const int32_t*)unit_task.data(), nu), arr_in(d_uw, unit_word_off, nu + 1), arr_in(d_us, unit_seq4_off, nu + 1), arr_in(d_un, unit_name_off, nu + 1),
         // (room for n + 1 offsets; without reads nothing comes back and the caller may pass neither seq4_off nor name_off)
         arr_out(d_seq4, seq4, (size_t)unit_seq4_off[n_units]), arr_out(d_s4off, seq4_off, n + 1, offs),
@@ -1095,9 +1061,8 @@ int tredgpu_genotype_selected(tredgpu_ctx* c, const tredgpu_selected_units* segs
                                                           d_off, d_len, d_seq4, d_s4off, d_names, d_nmoff, c->stream));
         g += segs[sgi].n_units;
     }
-    if (!rc) rc = run_fused_device(c, d_packed, d_off, d_len, n_reads, d_uoff, d_ulad, d_units, n_units, params, params->max_read_len,
-                                   nullptr, d_gl, d_tl, d_tag, d_h, d_score, hist_stride, d_f, d_p, d_r, d_calls, d_marg, marg_stride,
-                                   limits, d_joff, d_joint, d_jn, d_jt);
+    if (!rc) rc = run_fused_device(c, d_packed, d_off, d_len, n_reads, d_uoff, d_ulad, params, params->max_read_len, nullptr, d_tag, d_h,
+                                   d_score, d_f, d_p, d_r, a, limits);
     return finish(c, list, rc);
 }
 
@@ -1124,9 +1089,11 @@ int tredgpu_genotype_batch(tredgpu_ctx* c, int mem, const uint32_t* packed, cons
         int limits[2] = {0, 0};
         if (n_units > 0 && (rc = query_max_insert(c, units, n_units, limits))) return rc;
         if (read_pair_id && (rc = ensure(c, c->ws_drop, (size_t)n_reads))) return rc;
-        return run_fused_device(c, packed, read_off, read_len, n_reads, unit_read_off, unit_ladder, units, n_units, params, max_len,
-                                read_pair_id, global_lens, target_lens, out_tag, out_h, out_score, hist_stride, full_cnt, pref_cnt,
-                                rept_cnt, calls, nullptr, 0, limits);
+        GridArgs a = {};
+        a.units = units; a.n_units = n_units; a.hist_stride = hist_stride;
+        a.global_lens = global_lens; a.target_lens = target_lens; a.calls = calls;
+        return run_fused_device(c, packed, read_off, read_len, n_reads, unit_read_off, unit_ladder, params, max_len, read_pair_id, out_tag,
+                                out_h, out_score, full_cnt, pref_cnt, rept_cnt, a, limits);
     }
     if (mem != TREDGPU_MEM_HOST) return fail(c, -2, "bad mem");
     // HOST memory: compose the three host-memory calls (each validates and stages its own arguments)

@@ -6,7 +6,9 @@
 //   calc_PP :342-368, safe_log :418-423, PEMaxLikModel :426-473 (incl. scipy gaussian_kde).
 //
 // Four kernels per pass over the batch's units; every unit takes exactly the scratch it needs from one pool
-// (atomic bump allocation in 16 sub-pools; a unit that finds its sub-pool full is deferred to a further pass):
+// (atomic bump allocation in up to 16 sub-pools; a unit that finds its sub-pool full is deferred to a further pass).  The layout
+// of a unit's slot and every size of the workspace are grid_host.h's (unit_layout, plan_grid); the host hands the buffers over
+// as one GridWorkspace and launches a pass phase by phase (launch_grid_phase, at the end of this file):
 //   grid_kde_kernel      one workgroup per unit that has a paired-end model: is the term used (from the histograms),
 //                        then the KDE -- an fp64 convolution -- or, when it is not, only the singularity check
 //                        (first pass only)
@@ -55,21 +57,14 @@ constexpr int KDE_WAVES = GRID_KDE_WAVES, KDE_BLOCKS = 512 * GRID_KDE_WAVES;    
 constexpr int PREP_WAVES = GRID_PREP_WAVES, PREP_BLOCKS = 512 * GRID_PREP_WAVES;   // 128 VGPRs (3 waves: 1.16 ms per 30 000 units, 4 waves: 1.02)
 constexpr int XPER = (TREDGPU_SPAN + NT - 1) / NT;  // KDE x-values per thread
 constexpr int SPAN = TREDGPU_SPAN;
-constexpr int MAXOBS = 256;  // distinct FULL / PREF sizes per unit
-constexpr int MAXM = 768;    // marginal bins (repeat units)
+static_assert(SPAN == GRID_SPAN, "grid_host.h sizes the KDE buffer");
+// (MAXOBS, MAXM, Obs, SlotLayout, unit_layout, unit_items, TQ, CB, RG, TC, RS: grid_host.h)
 
 struct Axis {
     int nb;      // entries taken from the sorted base list
     int start;   // arithmetic part: start, start+period, ...
     int n;       // its length
     __device__ int size() const { return nb + n; }
-};
-
-struct Obs {
-    int fullK[MAXOBS], fullC[MAXOBS];
-    int partK[MAXOBS], partC[MAXOBS];
-    int base[MAXOBS + 1];
-    int nF, nP, nb;
 };
 
 __device__ __forceinline__ int axis_value(const Axis& ax, const int* base, int period, int idx) {
@@ -485,27 +480,6 @@ __device__ __forceinline__ bool better(const Best& x, const Best& y) {  // is x 
 
 constexpr int NR = 256;     // threads per workgroup of grid_reduce_kernel
 
-// Where one unit's tables live in the scratch pool (offsets in doubles from the unit's base)
-struct SlotLayout {
-    int32_t obs, rowoff, far1, far2, near1, near2, rept, roll1, roll2, ml, total;
-};
-__device__ inline SlotLayout unit_layout(int nrow, int ncol, int nt, bool run_pe, bool haploid, int dmax, int n_near) {
-    SlotLayout L;
-    int o = 0;
-    L.obs = o;    o += (int)((sizeof(Obs) + 7) / 8);
-    L.rowoff = o; o += (nrow + 2) / 2;
-    L.far1 = o;   o += nrow;
-    L.far2 = o;   o += nrow;
-    L.near1 = o;  o += nrow * n_near;
-    L.near2 = o;  o += nrow * n_near;
-    L.rept = o;   o += dmax + 1;
-    L.roll1 = o;  o += run_pe ? nrow * ((nt + 31) & ~31) : 0;   // rows padded to 32 entries
-    L.roll2 = o;  o += run_pe && !haploid ? ncol * nt : 0;
-    L.ml = o;     o += nrow * ncol;
-    L.total = (o + 15) & ~15;   // slots start on 128-byte lines
-    return L;
-}
-
 // Per-unit record handed from grid_prepare_kernel to the other two kernels.
 // status: the tredgpu_call status, or UNIT_DEFERRED (no room in the pool this pass), UNIT_SKIP (done in an
 // earlier pass)
@@ -524,6 +498,7 @@ struct UnitDesc {
     SlotLayout lay;
     int32_t item_base, n_items;
 };
+static_assert(sizeof(UnitDesc) == GRID_DESC_BYTES && sizeof(int) + sizeof(Best) == GRID_ITEM_BYTES, "plan_grid sizes the buffers");
 
 // Device-side counters of one pass (zeroed by the launch).
 // Every counter that many workgroups add to exists TQ times, each copy on its own 64-byte line, and unit g (work item
@@ -533,7 +508,6 @@ struct UnitDesc {
 // A workgroup starts at queue blockIdx % TQ and moves on when a queue runs dry (next_ticket): balancing stays dynamic.
 // The scratch pool is split the same way into PQ <= TQ sub-pools (bump allocation per sub-pool; PQ = 1 when a single
 // unit could need more than a TQ-th of the pool), the work-item list into TQ regions.
-constexpr int TQ = 16;
 struct CounterLine {
     int32_t v;
     int32_t pad[15];
@@ -548,7 +522,7 @@ struct GridCounters {
     CounterLine next_kde[TQ], next_prepare[TQ], next_reduce[TQ], next_item[TQ];
     CounterLine n_deferred;
 };
-static_assert(sizeof(CounterLine) == 64 && sizeof(CounterLine64) == 64 && sizeof(GridCounters) == 64 * (6 * TQ + 1), "counter block layout");
+static_assert(sizeof(CounterLine) == 64 && sizeof(CounterLine64) == 64 && sizeof(GridCounters) == GRID_COUNTER_BYTES, "counter block layout");
 
 // The next unit (or work item) of a kernel's ticket queues, n when all are taken.  Queue q hands out q, q + TQ, ...
 // (limit[q] entries when `limit` is given: the work items of a region); called by one thread per workgroup, which
@@ -567,16 +541,7 @@ __device__ __forceinline__ int next_ticket(CounterLine* queues, TicketState& ts,
 }
 static_assert((TQ & (TQ - 1)) == 0, "queue index wraps by masking");
 
-constexpr int CB = 64;    // columns per work item of grid_pairs_kernel: one lane owns one h2 for all the item's rows
-constexpr int RG = 128;   // rows per item
-constexpr int TC = 32;    // spanning pairs per pass over the rows (the lane's roll(h2) values stay in registers)
 static_assert(TC == 32, "roll1 rows are padded to 32 entries (unit_layout)");
-
-// short grids (up to RS rows): one item takes all the column blocks, so the unit is looked up once
-constexpr int RS = 16;
-__device__ __forceinline__ int unit_items(int nrow, int ncol) {
-    return nrow <= RS ? 1 : ((ncol + CB - 1) / CB) * ((nrow + RG - 1) / RG);
-}
 
 // A unit's parameters as wave-uniform values: the loads go through the vector path (the kernels store to
 // memory the compiler cannot tell apart), readfirstlane moves every field to a scalar register.
@@ -1586,80 +1551,36 @@ hipError_t launch_unit_max(const tredgpu_unit_params* units, int n_units, int* o
     return hipGetLastError();
 }
 
-size_t grid_desc_bytes() { return sizeof(UnitDesc); }
+const int32_t* grid_deferred(const GridWorkspace& w) { return &reinterpret_cast<const GridCounters*>(w.counters)->n_deferred.v; }
 
-size_t grid_counter_bytes() { return sizeof(GridCounters); }
-
-size_t grid_items_cap(int rows_cap, int cols_cap) {   // most work items one unit can make
-    return (size_t)((cols_cap + CB - 1) / CB) * ((rows_cap + RG - 1) / RG);
-}
-
-size_t grid_item_bytes() { return sizeof(int) + sizeof(Best); }
-
-// largest slot a unit within the caps can ask for (nt_max = most spanning pairs of any unit)
-size_t grid_slot_doubles_max(int rows_cap, int cols_cap, int nt_max) {
-    const size_t ntp = ((size_t)std::max(nt_max, 0) + 31) & ~(size_t)31;
-    return (sizeof(Obs) + 7) / 8 + (size_t)rows_cap * 3 + 2 + 2 * (size_t)18 * MAXM + 2 + (size_t)rows_cap * ntp +
-           (size_t)cols_cap * (size_t)std::max(nt_max, 0) + 3 * (size_t)rows_cap * cols_cap + 16;
-}
-
-// One pass over all units: prepare (takes pool room per unit) -> pairs -> reduce, all on stream s.  Units that
-// found the pool full are marked UNIT_DEFERRED in calls[].status and counted in the counter block's
-// n_deferred; the caller runs further passes (pass > 0 touches only those) until none is left.
-// items: item_cap ints (item -> unit), then item_cap arg-max records; item_cap = grid_item_slots(n_units, ...): TQ
-// regions.  pool_doubles is used as grid_subpools() sub-pools of equal size.
-hipError_t launch_grid_pass(const GridArgs& a, int pass, void* descs, double* pool, size_t pool_doubles, int rows_cap,
-                            int cols_cap, void* items, size_t item_cap, void* counters, hipStream_t s, int phases) {
-    // phases: bit 0 prepare (with the counter reset), bit 1 pairs, bit 2 reduce, bit 3 the paired-end KDEs (first, and
-    // in pass 0 only: deferred units keep theirs) -- the caller may launch them one by one to time each (capi.hip
-    // brackets them with HIP events)
-    if (a.n_units <= 0) return hipSuccess;
-    UnitDesc* d = (UnitDesc*)descs;
-    GridCounters* ctr = (GridCounters*)counters;
-    int* item_unit = (int*)items;
-    Best* item_best = (Best*)(item_unit + ((item_cap + 3) & ~(size_t)3));
-    const int item_region = (int)(item_cap / TQ);
-    const int n_sub = grid_subpools(pool_doubles, rows_cap, cols_cap, a.max_target);
-    const unsigned long long sub_doubles = (pool_doubles / n_sub) & ~(unsigned long long)15;   // slots start on 128-byte lines
-    if ((phases & 8) && pass == 0) {
-        hipError_t e = hipMemsetAsync(counters, 0, sizeof(GridCounters), s);
+hipError_t launch_grid_phase(const GridArgs& a, const GridWorkspace& w, int pass, GridPhase phase, hipStream_t s) {
+    if (a.n_units <= 0 || (phase == GridPhase::KDE && pass != 0)) return hipSuccess;
+    const GridPlan& p = w.plan;
+    UnitDesc* d = reinterpret_cast<UnitDesc*>(w.descs);
+    GridCounters* ctr = reinterpret_cast<GridCounters*>(w.counters);
+    int* item_unit = reinterpret_cast<int*>(w.items);
+    Best* item_best = reinterpret_cast<Best*>(item_unit + p.item_best);
+    if (phase == GridPhase::KDE || phase == GridPhase::PREPARE) {   // each starts from fresh ticket queues
+        hipError_t e = hipMemsetAsync(ctr, 0, sizeof(GridCounters), s);
         if (e != hipSuccess) return e;
-        const int kb = a.n_units < KDE_BLOCKS ? a.n_units : KDE_BLOCKS;
-        grid_kde_kernel<<<kb, NT, 0, s>>>(a, ctr);
     }
-    if (phases & 1) {
-        hipError_t e = hipMemsetAsync(counters, 0, sizeof(GridCounters), s);
-        if (e != hipSuccess) return e;
-        const int pb = a.n_units < PREP_BLOCKS ? a.n_units : PREP_BLOCKS;
-        grid_prepare_kernel<<<pb, NT, 0, s>>>(a, pass, d, pool, sub_doubles, n_sub, rows_cap, cols_cap, item_unit,
-                                              item_region, ctr);
-    }
-    if (phases & 2) grid_pairs_kernel<<<2048, 256, 0, s>>>(a, d, pool, item_unit, item_best, item_region, ctr);
-    if (phases & 4) {
-        const int rb = a.n_units < 2048 ? a.n_units : 2048;
-        if (a.joint != nullptr) grid_reduce_kernel<true><<<rb, NR, 0, s>>>(a, d, pool, item_best, ctr);
-        else grid_reduce_kernel<false><<<rb, NR, 0, s>>>(a, d, pool, item_best, ctr);
+    switch (phase) {
+    case GridPhase::KDE:
+        grid_kde_kernel<<<std::min(a.n_units, KDE_BLOCKS), NT, 0, s>>>(a, ctr);
+        break;
+    case GridPhase::PREPARE:
+        grid_prepare_kernel<<<std::min(a.n_units, PREP_BLOCKS), NT, 0, s>>>(a, pass, d, w.pool, p.sub_doubles, p.n_sub, p.cap, p.cap, item_unit,
+                                                                           p.item_region, ctr);
+        break;
+    case GridPhase::PAIRS:
+        grid_pairs_kernel<<<2048, 256, 0, s>>>(a, d, w.pool, item_unit, item_best, p.item_region, ctr);
+        break;
+    case GridPhase::REDUCE:
+        if (a.joint != nullptr) grid_reduce_kernel<true><<<std::min(a.n_units, 2048), NR, 0, s>>>(a, d, w.pool, item_best, ctr);
+        else grid_reduce_kernel<false><<<std::min(a.n_units, 2048), NR, 0, s>>>(a, d, w.pool, item_best, ctr);
+        break;
     }
     return hipGetLastError();
 }
-
-int grid_deferred_offset() { return (int)offsetof(GridCounters, n_deferred); }
-
-// Sub-pools the scratch pool is used as: as many (a power of two, at most TQ) as still leave room for the largest slot
-// in each -- a unit is never too big for its sub-pool, so every pass settles at least one unit per sub-pool.
-int grid_subpools(size_t pool_doubles, int rows_cap, int cols_cap, int nt_max) {
-    const size_t slot = grid_slot_doubles_max(rows_cap, cols_cap, nt_max) + 16;
-    int n = TQ;
-    while (n > 1 && pool_doubles / n < slot) n >>= 1;
-    return n;
-}
-
-// Entries of the work-item list for n_units units: TQ regions, each with room for the units of its queue
-size_t grid_item_slots(int n_units, int rows_cap, int cols_cap) {
-    return (size_t)TQ * (((size_t)n_units + TQ - 1) / TQ) * grid_items_cap(rows_cap, cols_cap);
-}
-
-// Units a sub-pool can be asked to hold at most (the units of one residue class mod the sub-pool count)
-size_t grid_units_per_subpool(int n_units, int n_sub) { return ((size_t)n_units + n_sub - 1) / n_sub; }
 
 }  // namespace tredgpu

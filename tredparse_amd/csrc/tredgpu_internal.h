@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/tredgpu.h"
+#include "grid_host.h"
 
 namespace tredgpu {
 
@@ -115,27 +116,36 @@ struct GridArgs {
     int32_t* kde_status;  // tredgpu_pe_kde only: [n_units]
     double* unit_pdf;      // grid passes: [n_units][1000] KDEs of the units whose paired-end term is used (grid_kde_kernel)
     int32_t* unit_kde_rc;  // grid passes: [n_units] outcome of the unit's KDE (0, -2, -6)
-    int32_t max_target;    // grid passes: largest n_target of the batch (bounds a unit's slot, grid_subpools)
+    int32_t max_target;    // grid passes: largest n_target of the batch (bounds a unit's slot, plan_grid)
 };
-constexpr int GRID_MAX_ROWS = 1024;  // |h1range| / |h2range| the grid kernels accept (status -5 beyond)
-constexpr int GRID_MAX_COLS = 1024;
 constexpr size_t GRID_POOL_BYTES = (size_t)12 << 30;  // scratch pool the units' tables are carved from
 constexpr int GRID_UNIT_DEFERRED = 100;               // calls[].status of a unit waiting for the next pass
 
 hipError_t launch_pe_kde(const GridArgs& a, hipStream_t s);
 // max over units of maxinsert -> out[0], of n_target -> out[1] (device ints, zeroed by the launch)
 hipError_t launch_unit_max(const tredgpu_unit_params* units, int n_units, int* out, hipStream_t s);
-size_t grid_desc_bytes();
-size_t grid_counter_bytes();
-int grid_deferred_offset();                          // byte offset of the deferred-unit count in the counter block
-size_t grid_slot_doubles_max(int rows_cap, int cols_cap, int nt_max);
-size_t grid_items_cap(int rows_cap, int cols_cap);   // work items one unit can make at most
-size_t grid_item_bytes();                            // bytes per work item in the items buffer
-size_t grid_item_slots(int n_units, int rows_cap, int cols_cap);   // entries of the work-item list (16 regions, one per ticket queue)
-int grid_subpools(size_t pool_doubles, int rows_cap, int cols_cap, int nt_max);   // sub-pools the scratch pool is used as
-size_t grid_units_per_subpool(int n_units, int n_sub);
-// One pass over all units (prepare -> pairs -> reduce); see grid.hip
-hipError_t launch_grid_pass(const GridArgs& a, int pass, void* descs, double* pool, size_t pool_doubles, int rows_cap,
-                            int cols_cap, void* items, size_t item_cap, void* counters, hipStream_t s, int phases = 15);
+
+// The scratch of a call's grid passes, sized by plan_grid (grid_host.h).  The records stay private to grid.hip:
+struct GridDescs;      // its UnitDesc per unit                             plan.desc_bytes
+struct GridItems;      // its work-item list: item -> unit, then the items' arg-max records   plan.items_bytes
+struct GridCounterBlock;   // its GridCounters of one pass                 plan.counter_bytes
+struct GridWorkspace {
+    GridPlan plan;
+    GridDescs* descs;
+    double* pool;          // plan.pool_bytes
+    GridItems* items;
+    GridCounterBlock* counters;
+    double* kde_pdf;       // GridArgs.unit_pdf: plan.kde_pdf_bytes, and behind them ...
+    int32_t* kde_rc;       // ... GridArgs.unit_kde_rc
+};
+// the deferred-unit count (one device int) in the counter block
+const int32_t* grid_deferred(const GridWorkspace& w);
+// One phase of a pass over all units, on stream s (the caller brackets each with HIP events): the paired-end KDEs
+// (pass 0 only: deferred units keep theirs), then prepare (takes pool room per unit) -> pairs -> reduce.  KDE and PREPARE
+// clear the counter block first.  Units that found their sub-pool full are marked GRID_UNIT_DEFERRED in calls[].status and
+// counted in grid_deferred(); the caller runs further passes (pass > 0 touches only those) until none is left.
+enum class GridPhase { KDE = TREDGPU_KERNEL_GRID_KDE, PREPARE = TREDGPU_KERNEL_GRID_PREPARE, PAIRS = TREDGPU_KERNEL_GRID_PAIRS,
+                       REDUCE = TREDGPU_KERNEL_GRID_REDUCE };   // (the values: tredgpu_get_timing's series)
+hipError_t launch_grid_phase(const GridArgs& a, const GridWorkspace& w, int pass, GridPhase phase, hipStream_t s);
 
 }  // namespace tredgpu
