@@ -115,6 +115,12 @@ SCAN_TILE = 4096                # TREDSCAN_TILE: the letters one wavefront owns
 SCAN_MAX_LETTERS = 1 << 30      # TREDSCAN_MAX_LETTERS: the letters of all segments of one call
 SCAN_MIN_COPIES = (10, 6, 5, 4, 4, 4)      # whole copies a run of period 1 .. 6 needs to be reported: a choice, not a measurement
 
+# the interrupted-tract scan's symbols (include/tredtract.h)
+TRACT_EXPORTS = ("tredtract_scan", "tredtract_get_timing", "tredtract_reset_timing", "tredtract_release", "tredtract_last_error")
+TRACT_MAX_GAP = 64              # TREDTRACT_MAX_GAP: the most letters between two linked seeds
+TRACT_SEED_COPIES = (5, 3, 3, 3, 3, 3)     # whole copies a perfect run of period 1 .. 6 needs to take part: a choice, not a measurement
+TRACT_MAX_GAP_DEFAULT = (1, 2, 3, 4, 5, 6)  # letters between two seeds that are joined (one unit): a choice, not a measurement
+
 # every symbol include/tredgpu.h declares (tests check the .so exports them all)
 EXPORTS = ("tredgpu_create", "tredgpu_destroy", "tredgpu_last_error", "tredgpu_sync", "tredgpu_get_stream",
            "tredgpu_version", "tredgpu_set_ladders", "tredgpu_set_model", "tredgpu_pack_reads",
@@ -135,6 +141,7 @@ KERNEL_PILEUP = 19              # tredpileup_get_timing (include/tredpileup.h): 
 KERNEL_TRIO = 20                # tredtrio_get_timing (include/tredtrio.h): calls of trio and their device time
 KERNEL_COHORT = 21              # tredcohort_get_timing (include/tredcohort.h): calls of cohort and their device time
 KERNEL_SCAN = 22                # tredscan_get_timing (include/tredscan.h): calls of scan and their device time
+KERNEL_TRACT = 23               # tredtract_get_timing (include/tredtract.h): calls of scan_tracts and their device time
 
 
 # the timed opt-in units: (prefix, get-timing, reset-timing, KERNEL_* selector, last_error), in the order reset_timing has
@@ -147,7 +154,8 @@ SIDE_UNITS = (("tredlong", "tredlong_cigar_timing", "tredlong_cigar_reset_timing
               ("tredpileup", "tredpileup_get_timing", "tredpileup_reset_timing", KERNEL_PILEUP, "tredpileup_last_error"),
               ("tredtrio", "tredtrio_get_timing", "tredtrio_reset_timing", KERNEL_TRIO, "tredtrio_last_error"),
               ("tredcohort", "tredcohort_get_timing", "tredcohort_reset_timing", KERNEL_COHORT, "tredcohort_last_error"),
-              ("tredscan", "tredscan_get_timing", "tredscan_reset_timing", KERNEL_SCAN, "tredscan_last_error"))
+              ("tredscan", "tredscan_get_timing", "tredscan_reset_timing", KERNEL_SCAN, "tredscan_last_error"),
+              ("tredtract", "tredtract_get_timing", "tredtract_reset_timing", KERNEL_TRACT, "tredtract_last_error"))
 
 _lib = None
 
@@ -185,6 +193,7 @@ def load():
     lib.tredtrio_evaluate.argtypes = [vp, C.POINTER(TrioParams), i64] + [vp] * 19
     lib.tredcohort_evaluate.argtypes = [vp, C.POINTER(CohortParams), i64] + [vp] * 16
     lib.tredscan_scan.argtypes = [vp, vp, vp, i32, vp, i64, vp, vp, vp, vp, C.POINTER(i64)]
+    lib.tredtract_scan.argtypes = [vp, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
     for prefix, get_timing, reset_timing, _, last_error in SIDE_UNITS:
         getattr(lib, get_timing).argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double)]
         getattr(lib, reset_timing).argtypes = [vp]
@@ -768,6 +777,34 @@ class Context:
         self._chk_side(rc, "tredscan_scan failed ({})".format(rc), self.lib.tredscan_last_error)
         n = min(total.value, room)
         return seg[:n], start[:n], length[:n], period[:n], total.value
+
+    def scan_tracts(self, letters, seg_off, min_copies=SCAN_MIN_COPIES, seed_copies=TRACT_SEED_COPIES, max_gap=TRACT_MAX_GAP_DEFAULT,
+                    cap=1 << 16):
+        """tredtract_scan (include/tredtract.h): the interrupted tandem repeats of the segments seg_off (int64 [n_seg + 1])
+        of letters (bytes or a uint8 array), host memory.  Perfect runs of seed_copies whole copies and more (the seeds) of
+        one motif in one phase are joined across at most max_gap letters; a tract of min_copies whole copies is a record
+        (per period 1 .. 6; a min_copies of 0 switches the period off).  The defaults are a choice, not a measurement.
+        Returns (seg int32, start int64, length int32, period int32, seeds int32, mismatch int32, total): the first
+        min(total, cap) records in ascending (seg, start, period) order; total is what there is, also above cap."""
+        buf = np.frombuffer(letters, np.uint8) if not isinstance(letters, np.ndarray) else letters
+        off = np.ascontiguousarray(seg_off, np.int64)
+        mc, sc, mg = (np.ascontiguousarray(x, np.int32) for x in (min_copies, seed_copies, max_gap))
+        if buf.dtype != np.uint8 or off.ndim != 1 or len(off) < 1 or any(x.shape != (SCAN_MAX_PERIOD,) for x in (mc, sc, mg)):
+            raise ValueError("scan_tracts: letters are bytes, seg_off has n_seg + 1 entries, min_copies, seed_copies and max_gap "
+                             "have {} each".format(SCAN_MAX_PERIOD))
+        if len(buf) < off[-1]:
+            raise ValueError("scan_tracts: seg_off ends at {} but there are {} letters".format(int(off[-1]), len(buf)))
+        cap = int(cap)
+        room = max(cap, 0)
+        start = np.empty(room, np.int64)
+        seg, length, period, seeds, mismatch = (np.empty(room, np.int32) for _ in range(5))
+        total = C.c_int64(0)
+        rc = self.lib.tredtract_scan(self.h, _ptr(buf) if len(buf) else None, _ptr(off), len(off) - 1, _ptr(mc), _ptr(sc), _ptr(mg),
+                                     cap, _ptr(seg), _ptr(start), _ptr(length), _ptr(period), _ptr(seeds), _ptr(mismatch),
+                                     C.byref(total))
+        self._chk_side(rc, "tredtract_scan failed ({})".format(rc), self.lib.tredtract_last_error)
+        n = min(total.value, room)
+        return seg[:n], start[:n], length[:n], period[:n], seeds[:n], mismatch[:n], total.value
 
     def reset_timing(self):
         self._chk(self.lib.tredgpu_reset_timing(self.h), "tredgpu_reset_timing")

@@ -787,14 +787,16 @@ class Engine(object):
         return results_of(n, item_off, samples, ploidy, allele_off, members, out, tol)
 
     # ---- where the repeats are ----------------------------------------------------------------------
-    def scan_repeats(self, segments, min_copies=None, periods=None):
+    def scan_repeats(self, segments, min_copies=None, periods=None, interruptions=None):
         """The perfect tandem repeats of `segments` (bytes-like letter sequences) on this engine's context, as (seg, start,
         length, period) arrays in ascending (seg, start, period) order: prepare.scan_repeats, which batches the segments
         into Context.scan calls and joins the runs of a segment longer than one call (the definition: DESIGN.md 4,
         "Tandem-repeat scan").  min_copies: per period 1 .. 6, _lib.SCAN_MIN_COPIES by default -- a choice, not a
-        measurement; periods: the periods to report, all by default."""
+        measurement; periods: the periods to report, all by default.  interruptions: None for the perfect repeats;
+        (seed_copies, max_gap), or True for _lib.TRACT_SEED_COPIES and _lib.TRACT_MAX_GAP_DEFAULT (a choice too), for the
+        interrupted tracts of Context.scan_tracts ("Interrupted tracts"): the return gains seeds and mismatch."""
         from .prepare import scan_repeats
-        return scan_repeats(self.ctx, segments, min_copies=min_copies, periods=periods)
+        return scan_repeats(self.ctx, segments, min_copies=min_copies, periods=periods, interruptions=interruptions)
 
     # ---- the whole path ------------------------------------------------------------------------------
     def genotype(self, units, want_grid=True):

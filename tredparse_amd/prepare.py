@@ -1,6 +1,6 @@
 """Loci of your own from a reference FASTA: `python -m tredparse_amd.prepare locus` cuts the flanks of one locus and writes
-its site file, `python -m tredparse_amd.prepare scan` finds the perfect tandem repeats of a FASTA on the GPU and writes them
-as a catalogue (and, on request, as site files).
+its site file, `python -m tredparse_amd.prepare scan` finds the tandem repeats of a FASTA on the GPU -- the perfect ones, or
+with --interruptions those that substitutions interrupt -- and writes them as a catalogue (and, on request, as site files).
 
 The site files are the reference's schema (its sites/README.md; meta.TREDsRepo(sites=...) loads them, tred.py --sites DIR
 points at them).  The reference's own tool asks its questions on the terminal, needs pyfaidx and writes "repeat": "CAG"
@@ -10,6 +10,11 @@ The scan is include/tredscan.h (Context.scan): the maximal runs of every period 
 and a primitive motif.  The min_copies defaults (_lib.SCAN_MIN_COPIES: 10, 6, 5, 4, 4, 4) are a choice, not a measurement.
 Genotyping at catalogue scale -- thousands of scanned loci in one tred.py run, alternative regions for user loci, cut-offs
 derived from data -- is out of scope: a scanned site carries placeholder cut-offs.
+
+`scan --interruptions` is include/tredtract.h (Context.scan_tracts): perfect runs of seed_copies copies of one motif in one
+phase are joined across at most max_gap substituted letters, so (CGG)9 AGG (CGG)9 AGG (CGG)10 is one row of 30 copies with
+2 mismatches, not three.  Its defaults (_lib.TRACT_SEED_COPIES: 5, 3, 3, 3, 3, 3; _lib.TRACT_MAX_GAP_DEFAULT: 1 .. 6, one
+unit) are a choice, not a measurement either.  A lone unit behind an interruption is not absorbed, and indels end a tract.
 """
 import argparse
 import json
@@ -26,6 +31,7 @@ FLANK = 18
 _COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
 _STRIP = b"\r\n"
 CATALOG_COLUMNS = ("contig", "start", "end", "period", "motif", "copies", "partial", "canonical", "prefix", "suffix")
+TRACT_COLUMNS = CATALOG_COLUMNS + ("seeds", "mismatches", "purity")     # the catalogue of scan --interruptions
 # every column of a site file (the reference's sites/PIEZO1.json); what the tool cannot know stays ""
 SITE_COLUMNS = ("allele_freq", "cutoff_prerisk", "cutoff_risk", "gene_location", "gene_name", "gene_part", "id", "inheritance",
                 "motif", "mutation_nature", "normal", "omim_id", "prefix", "prerisk", "repeat", "repeat_location",
@@ -146,15 +152,67 @@ def _min_copies(min_copies, periods):
     return [int(m) for m in mc]
 
 
-def scan_repeats(ctx, segments, min_copies=None, periods=None, max_letters=_lib.SCAN_MAX_LETTERS, cap=1 << 16):
+def _tract_params(mc, interruptions):
+    """(seed_copies, max_gap) of scan_repeats' `interruptions` (True: the defaults), checked against include/tredtract.h's
+    rules for the periods that are on."""
+    sc, mg = (_lib.TRACT_SEED_COPIES, _lib.TRACT_MAX_GAP_DEFAULT) if interruptions is True else interruptions
+    sc, mg = list(sc), list(mg)
+    if len(sc) != _lib.SCAN_MAX_PERIOD or len(mg) != _lib.SCAN_MAX_PERIOD or any(int(x) != x for x in sc + mg):
+        raise PrepareError("seed_copies and max_gap: {} whole numbers each".format(_lib.SCAN_MAX_PERIOD))
+    for p, (m, c, g) in enumerate(zip(mc, sc, mg), 1):
+        if m == 0:
+            continue
+        if not 2 <= c <= m:
+            raise PrepareError("period {}: 2 <= seed_copies <= min_copies does not hold (seed_copies {}, min_copies {})".format(p, c, m))
+        if not 0 <= g <= _lib.TRACT_MAX_GAP:
+            raise PrepareError("period {}: 0 <= max_gap <= {} does not hold (max_gap {})".format(p, _lib.TRACT_MAX_GAP, g))
+        if not c * p > g + 2 * p - 2:
+            raise PrepareError("period {}: seed_copies * p > max_gap + 2 p - 2 does not hold ({} * {} <= {} + {}): longer seeds or "
+                               "a smaller gap".format(p, c, p, g, 2 * p - 2))
+    return [int(c) for c in sc], [int(g) for g in mg]
+
+
+def _scan_tracts(ctx, segments, mc, interruptions, max_letters, cap):
+    """scan_repeats' tract path: the segments batched into Context.scan_tracts calls of at most max_letters letters."""
+    sc, mg = _tract_params(mc, interruptions)
+    bufs = [letters if isinstance(letters, np.ndarray) else np.frombuffer(letters, np.uint8) for letters in segments]
+    for k, buf in enumerate(bufs):
+        if len(buf) > max_letters:
+            raise PrepareError("segment {} has {} letters, more than the {} of one call: tracts are not joined across a cut "
+                               "(scan it in regions, or without --interruptions)".format(k, len(buf), max_letters))
+    found = []
+    i = 0
+    while i < len(bufs):
+        j, letters = i, 0
+        while j < len(bufs) and (j == i or letters + len(bufs[j]) <= max_letters):
+            letters += len(bufs[j])
+            j += 1
+        buf = bufs[i] if j == i + 1 else np.concatenate(bufs[i:j])
+        off = np.concatenate(([0], np.cumsum([len(b) for b in bufs[i:j]]))).astype(np.int64)
+        out = ctx.scan_tracts(buf, off, mc, sc, mg, cap)
+        if out[6] > len(out[0]):
+            out = ctx.scan_tracts(buf, off, mc, sc, mg, out[6])
+        found.append(np.stack([out[0].astype(np.int64) + i] + [x.astype(np.int64) for x in out[1:6]], axis=1).reshape(-1, 6))
+        i = j
+    rows = np.concatenate(found) if found else np.zeros((0, 6), np.int64)
+    return (rows[:, 0].astype(np.int32), rows[:, 1].copy()) + tuple(rows[:, k].astype(np.int32) for k in range(2, 6))
+
+
+def scan_repeats(ctx, segments, min_copies=None, periods=None, max_letters=_lib.SCAN_MAX_LETTERS, cap=1 << 16, interruptions=None):
     """The tandem repeats of `segments` (bytes-like letter sequences) by Context.scan, as (seg int32, start int64, length
     int32, period int32) in ascending (seg, start, period) order -- what one call on all segments would give, whatever
     their sizes.  Segments are batched into calls of at most max_letters letters.  A longer segment is cut into pieces that
     overlap by the longest run that just qualifies (max of min_copies p, and no less than the longest period): a run that
     crosses a cut qualifies in the piece on either side, two pieces of one run share at least p letters -- which two
     different runs of period p never do -- and are joined by that.  A call whose records exceed `cap` is repeated with
-    room for all of them."""
+    room for all of them.
+    interruptions: None for the above; (seed_copies, max_gap), or True for the defaults (a choice, not a measurement), for
+    the interrupted tracts of Context.scan_tracts (include/tredtract.h): the return gains seeds and mismatch (int32), the
+    segments are batched in the same way, and a segment longer than max_letters is refused -- tracts are not joined
+    across a cut."""
     mc = _min_copies(min_copies, periods)
+    if interruptions is not None:
+        return _scan_tracts(ctx, segments, mc, interruptions, max_letters, cap)
     overlap = max([m * p for p, m in enumerate(mc, 1)] + [_lib.SCAN_MAX_PERIOD])
     if max_letters < 2 * overlap + 2:
         raise PrepareError("max_letters {} is too small for runs of {} letters".format(max_letters, overlap))
@@ -291,9 +349,11 @@ def parse_regions(fasta, regions):
 
 def catalog_rows(fasta, regions, records, flank=FLANK):
     """The records of scan_repeats over parse_regions' regions as the rows of the catalogue (CATALOG_COLUMNS): 1-based
-    start, end of the whole copies; the flanks are the contig's, '' where one would leave it."""
+    start, end of the whole copies; the flanks are the contig's, '' where one would leave it.  Records of the tract path
+    (six arrays) give TRACT_COLUMNS: end, copies and partial from the tract's length, the motif the letters at its start
+    (the first seed's, in phase), then seeds, mismatches and purity = 1 - mismatches / length."""
     rows = []
-    for seg, start, length, period in zip(*records):
+    for seg, start, length, period, *tract in zip(*records):
         contig, a, _ = regions[seg]
         g, p = a + int(start), int(period)                  # 0-based in the contig
         copies, partial = divmod(int(length), p)
@@ -302,12 +362,15 @@ def catalog_rows(fasta, regions, records, flank=FLANK):
         prefix = suffix = ""
         if g >= flank and end + flank <= fasta.length(contig):
             prefix, suffix = fasta.fetch(contig, g - flank, g).decode(), fasta.fetch(contig, end, end + flank).decode()
-        rows.append((contig, g + 1, end, p, motif, copies, partial, canonical_motif(motif), prefix, suffix))
+        row = (contig, g + 1, end, p, motif, copies, partial, canonical_motif(motif), prefix, suffix)
+        if tract:
+            row += (int(tract[0]), int(tract[1]), "%.4f" % (1 - int(tract[1]) / int(length)))
+        rows.append(row)
     return rows
 
 
-def catalog_text(rows):
-    return "".join("\t".join(str(x) for x in row) + "\n" for row in [("#" + CATALOG_COLUMNS[0],) + CATALOG_COLUMNS[1:]] + list(rows))
+def catalog_text(rows, columns=CATALOG_COLUMNS):
+    return "".join("\t".join(str(x) for x in row) + "\n" for row in [("#" + columns[0],) + columns[1:]] + list(rows))
 
 
 def write_catalog_sites(rows, outdir, max_sites):
@@ -343,6 +406,15 @@ def set_argparse():
     s.add_argument("--periods", default="1-6", help="periods to report, e.g. 1-6 or 2,3")
     s.add_argument("--min-copies", dest="min_copies", default=",".join(str(m) for m in _lib.SCAN_MIN_COPIES),
                    help="whole copies a run of period 1,2,..,6 needs; the defaults are a choice, not a measurement")
+    s.add_argument("--interruptions", action="store_true",
+                   help="join perfect runs of one motif and phase across substituted letters (include/tredtract.h); the catalogue "
+                        "gains the columns seeds, mismatches and purity")
+    s.add_argument("--seed-copies", dest="seed_copies", default=None, metavar=",".join(str(c) for c in _lib.TRACT_SEED_COPIES),
+                   help="whole copies a perfect run of period 1,2,..,6 needs to take part; implies --interruptions; the defaults "
+                        "are a choice, not a measurement")
+    s.add_argument("--max-gap", dest="max_gap", default=None, metavar=",".join(str(g) for g in _lib.TRACT_MAX_GAP_DEFAULT),
+                   help="letters between two runs that are joined, per period; implies --interruptions; the defaults (one unit) "
+                        "are a choice, not a measurement")
     s.add_argument("--flank", type=int, default=FLANK, help="letters of prefix and suffix")
     s.add_argument("--out", required=True, help="the catalogue is written to <out>.tsv")
     s.add_argument("--write-sites", dest="write_sites", default=None, metavar="DIR", help="also write one site file per record with flanks")
@@ -378,11 +450,19 @@ def run_scan(args, ctx=None):
         except ValueError:
             raise PrepareError("--min-copies: six counts, e.g. 10,6,5,4,4,4")
         periods = parse_periods(args.periods)
-        _min_copies(mc, periods)
+        on = _min_copies(mc, periods)
+        interruptions = None
+        if args.interruptions or args.seed_copies is not None or args.max_gap is not None:
+            try:
+                interruptions = tuple(list(default) if text is None else [int(x) for x in text.split(",")] for text, default in
+                                      ((args.seed_copies, _lib.TRACT_SEED_COPIES), (args.max_gap, _lib.TRACT_MAX_GAP_DEFAULT)))
+            except ValueError:
+                raise PrepareError("--seed-copies and --max-gap: six counts each, e.g. 5,3,3,3,3,3 and 1,2,3,4,5,6")
+            _tract_params(on, interruptions)               # (refused before a context is made)
         own = ctx is None
         ctx = _lib.Context(args.gpu) if own else ctx
         try:
-            records = scan_repeats(ctx, [fasta.fetch(c, a, b) for c, a, b in regions], mc, periods)
+            records = scan_repeats(ctx, [fasta.fetch(c, a, b) for c, a, b in regions], mc, periods, interruptions=interruptions)
         finally:
             if own:
                 ctx.close()
@@ -390,8 +470,8 @@ def run_scan(args, ctx=None):
     finally:
         fasta.close()
     with open(args.out + ".tsv", "w") as fp:
-        fp.write(catalog_text(rows))
-    print("{}.tsv: {} repeats".format(args.out, len(rows)), file=sys.stderr)
+        fp.write(catalog_text(rows, CATALOG_COLUMNS if interruptions is None else TRACT_COLUMNS))
+    print("{}.tsv: {} {}".format(args.out, len(rows), "repeats" if interruptions is None else "tracts"), file=sys.stderr)
     if args.write_sites:
         paths = write_catalog_sites(rows, args.write_sites, args.max_sites)
         print("{}: {} site files with placeholder cut-offs (reference copies + 1, AD, increase)".format(args.write_sites, len(paths)),
