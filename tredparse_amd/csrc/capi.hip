@@ -41,7 +41,7 @@ struct tredgpu_ctx {
     Buf d_model;
     bool have_model = false;
     // workspaces (grow-only, reused across calls)
-    Buf ws_quads, ws_counter, ws_drop, ws_stats, ws_perm, ws_class, ws_ucnt, ws_bins, ws_best, ws_cnt;
+    Buf ws_quads, ws_counter, ws_drop, ws_stats, ws_perm, ws_class, ws_ucnt, ws_bins, ws_best, ws_cnt, ws_tail;
     // the likelihood grid's: what plan_grid (grid_host.h) sizes, and the two ints of query_max_insert
     struct GridBufs { Buf pool, descs, items, counters, kde, unit_max; } grid;
     int* h_pin = nullptr;  // pinned word for small read-backs
@@ -394,7 +394,7 @@ void tredgpu_destroy(tredgpu_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)stream_sync(c);
     for (Buf* b : {&c->d_ladders, &c->d_seq, &c->d_model, &c->ws_quads, &c->ws_counter, &c->ws_drop,
-                   &c->ws_stats, &c->ws_perm, &c->ws_class, &c->ws_ucnt, &c->ws_bins, &c->ws_best, &c->ws_cnt, &c->grid.pool, &c->grid.descs,
+                   &c->ws_stats, &c->ws_perm, &c->ws_class, &c->ws_ucnt, &c->ws_bins, &c->ws_best, &c->ws_cnt, &c->ws_tail, &c->grid.pool, &c->grid.descs,
                    &c->grid.items, &c->grid.counters, &c->grid.kde, &c->grid.unit_max})
         release(*b);
     for (Buf& b : c->st) release(b);
@@ -628,8 +628,11 @@ static int run_sw_device(tredgpu_ctx* c, const uint32_t* packed, const int64_t* 
     if ((rc = ensure(c, c->ws_bins, sw_bin_bytes(n_ladders)))) return rc;
     if ((rc = ensure(c, c->ws_best, (size_t)n_reads * sizeof(int32_t)))) return rc;
     if ((rc = ensure(c, c->ws_cnt, (size_t)n_reads * sizeof(int32_t)))) return rc;
+    // the reads' per-lane tail counts: 16 bytes per strand (kmer_host.h)
+    if ((rc = ensure(c, c->ws_tail, (size_t)n_reads * 2 * kmer_host::TAIL_LANES))) return rc;
     a.best = (int32_t*)c->ws_best.p;
     a.read_cnt = (const int32_t*)c->ws_cnt.p;
+    a.read_tail = (uint8_t*)c->ws_tail.p;
     if (c->ws_stats.p == nullptr) {
         if ((rc = ensure(c, c->ws_stats, SW_STAT_SLOTS * 8 * sizeof(unsigned long long)))) return rc;
         HIPCHK(c, hipMemsetAsync(c->ws_stats.p, 0, SW_STAT_SLOTS * 8 * sizeof(unsigned long long), c->stream));

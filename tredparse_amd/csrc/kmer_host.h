@@ -1,5 +1,6 @@
 // kmer_host.h -- the 6-mer tables of one ladder strand, built on the host (tredgpu_set_ladders) for the exact strand
-// filter of sw_cont_kernel / read_class_kernel.  Plain C++17, no HIP (tests/kmer_weight_main.cpp runs it under ASan).
+// filter of sw_cont_kernel / read_class_kernel, and the arithmetic of the per-lane tail counts (below; host and device).
+// Plain C++17, no HIP needed (tests/kmer_weight_main.cpp and tests/sw_tail_main.cpp run it under ASan).
 //
 // Templates of a strand: head + repeat * u + branch, u = 1 .. max_units, as base codes 0..3 and 4 = N.  A template N
 // scores 0 against every base, so it neither breaks nor feeds a run of matches: a template window with N positions
@@ -64,6 +65,44 @@ inline bool build_tables(const Vec& head, const Vec& repeat, const Vec& branch, 
             if (fewest[w] != 15) cls[w >> 3] |= (uint32_t)fewest[w] << (4 * (w & 7));
     }
     return with_n;
+}
+
+// ---- per-lane tail counts (read_class_kernel -> SwArgs::read_tail -> the second tier of sw_cont_kernel's bounded-gain exit)
+// Wtail[lane] = the read's 6-mer windows that start at or after row lane * R and are present in the strand's templates (a
+// window with a read N counts as present), R = rows per lane; one byte per lane, saturated at TAIL_SAT; TAIL_NONE = no bound.
+// read_class_kernel's count loop has, per 16-base word of the read, the mask of the present windows by END position (a
+// window that starts at row w ends at w + 5); it leaves one entry per word, and the 16 counts are taken from the entries
+// once the loop is over.  Host and device: the same function is checked by tests/sw_tail_main.cpp under ASan.
+#if defined(__HIPCC__)
+#define KMER_HD __host__ __device__
+#else
+#define KMER_HD
+#endif
+constexpr int TAIL_LANES = 16;
+constexpr int TAIL_SAT = 254;
+constexpr int TAIL_NONE = 255;
+
+// One word's entry: the mask of its 16 end positions | the windows counted in the words before it << 16.
+KMER_HD inline uint32_t tail_entry(uint32_t end_mask, int before) { return (end_mask & 0xffffu) | (uint32_t)before << 16; }
+
+// entries[w * stride], w = 0 .. nb - 1; total = the windows counted in all words.  The lane's count = total - the windows
+// that end before position lane * R + 5.
+KMER_HD inline int tail_count(const uint32_t* entries, int stride, int nb, int total, int R, int lane) {
+    const int e = lane * R + 5;
+    const int w = e >> 4;
+    if (w >= nb) return 0;
+    const uint32_t en = entries[w * stride];
+    const int t = total - (int)(en >> 16) - __builtin_popcount(en & ((1u << (e & 15)) - 1u));
+    return t > TAIL_SAT ? TAIL_SAT : t;
+}
+
+// The 16 bytes of one read and strand, lane 0 in the low byte of out[0].
+KMER_HD inline void tail_pack(const uint32_t* entries, int stride, int nb, int total, int R, uint32_t out[4]) {
+    for (int k = 0; k < 4; ++k) {
+        uint32_t v = 0;
+        for (int b = 0; b < 4; ++b) v |= (uint32_t)tail_count(entries, stride, nb, total, R, 4 * k + b) << (8 * b);
+        out[k] = v;
+    }
 }
 
 }  // namespace kmer_host

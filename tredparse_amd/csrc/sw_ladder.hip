@@ -28,6 +28,7 @@
 //    only at template ends that are really combined); the (key, start) maximum of a template end's 2R candidates
 //    is taken by 64-bit LDS max atomics on a slot of the lane's own.  No lane reads another lane's slots.
 #include "tredgpu_internal.h"
+#include "kmer_host.h"
 
 namespace tredgpu {
 namespace {
@@ -38,10 +39,17 @@ constexpr int PAYMASK = KONE - 1;
 constexpr int NEG = -(1 << 30);
 constexpr int PADNEG = -64 * KONE;
 constexpr int CNT_UNFILTERED = 0x7FFF;   // stored 6-mer weight of a read the filter does not apply to
-// The bounded-gain test of steady_exit (sw_cont_kernel); -DSW_EXIT_BOUND=0 compiles it out (the Makefile builds that
-// kernel into libtredgpu_noexit.so, and tests/test_sw_exit_gpu.py compares the columns swept by the two libraries).
+// The bounded-gain test of steady_exit (sw_cont_kernel): 0 = compiled out, 1 = its first tier only (the gain bound from
+// the read rows left), 2 = both tiers (also the bound from the lane's tail count, SwArgs::read_tail).  The Makefile builds
+// the kernels of 0 and 1 into libtredgpu_noexit.so and libtredgpu_tier1.so; tests/test_sw_exit_gpu.py and
+// tests/test_sw_exit_tier2_gpu.py compare the columns swept by the library with those.
 #ifndef SW_EXIT_BOUND
-#define SW_EXIT_BOUND 1
+#define SW_EXIT_BOUND 2
+#endif
+// 1: a failed bounded-gain test falls through to the two-boundary test, as it did before the latter was shown dead there
+// (steady_exit has the argument); only for timing the two against each other.
+#ifndef SW_EXIT_FALLTHROUGH
+#define SW_EXIT_FALLTHROUGH 0
 #endif
 
 // The 6-mer weight of a read on a strand and the score cap it gives (sw_cont_kernel's strand filter has the argument
@@ -864,13 +872,42 @@ __global__ __launch_bounds__(64, W) void sw_cont_kernel(SwArgs a) {
                 const int need = max(max(min(L, alen + period * u + blen) >> 1, 30), u >= bestU ? bestS + 1 : bestS);
                 int nt = (L - 1 - r0) * mK - need * KONE - (r0 + c) * geK;   // -thr(first row of the lane)
                 uint32_t lo = 0x3FFFFu;
+#if SW_EXIT_BOUND >= 2
+                // Second tier: G(row) = match * min(L - 1 - row, 5 + Wtail), Wtail = the read's present 6-mer windows that
+                // start at or after the lane's first row (the strand filter's run argument for the rest of the path below
+                // `row`: its runs of matches use distinct windows that start at or after `row`, a break costs >= 5 matches;
+                // DESIGN.md 4.1).  read_class_kernel left the byte in a.read_tail, 255 where the premise does not hold; it is
+                // loaded here, at the test -- a value kept from the strand's entry cost the column blocks a register.
+                // The second bound has a running threshold of its own, which steps by ge alone; the row's is the smaller.
+                // (5 + Wtail capped at L: 255 then gives the first tier, and the product stays inside the range the host
+                //  checked for L * match.)
+                const int lnx = lane_now();
+                const int wt = (lnx >> 4) < q_count ? (int)a.read_tail[((int64_t)a.perm[q_first + (lnx >> 4)] * 2 + s) * kmer_host::TAIL_LANES + (lnx & 15)]
+                                                    : kmer_host::TAIL_NONE;
+                int nt2 = min(5 + wt, L) * mK - need * KONE - (r0 + c) * geK;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int t = min(nt, nt2);
+                    lo = min(lo, min((uint32_t)(H[r] + t) & 0x8003FE00u, (uint32_t)(E[r] + t - geK) & 0x8003FE00u));
+                    nt -= mK + geK;
+                    nt2 -= geK;
+                    asm volatile("" : "+v"(nt), "+v"(nt2), "+v"(lo));   // (row by row: computed ahead, the thresholds of all rows are live at once)
+                }
+#else
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     lo = min(lo, min((uint32_t)(H[r] + nt) & 0x8003FE00u, (uint32_t)(E[r] + nt - geK) & 0x8003FE00u));
                     nt -= mK + geK;
                     asm volatile("" : "+v"(nt), "+v"(lo));   // (row by row: computed ahead, the thresholds of all rows are live at once)
                 }
+#endif
                 if (__builtin_amdgcn_ballot_w64(lo < ((uint32_t)(alen + period) << 9)) == 0) return true;
+#if !SW_EXIT_FALLTHROUGH
+                // The two-boundary test below cannot fire here: it answers true only when every entry records a start
+                // >= alen + period, which is clause (a) of the test that has just failed; the ok_run it would set is read
+                // at a later boundary only, and there this test is asked first again (an arg-max stays).
+                return false;
+#endif
             }
 #endif
             const uint32_t thr = (uint32_t)(alen + (ok_run ? period : 0)) << 9;
@@ -994,8 +1031,13 @@ __device__ __forceinline__ void claim_bin_runs(const int* hist, int lad, int g, 
 // NCLS (a ladder with an N in its templates): kc = the two strands' class tables (2 x 512 words of 4-bit entries, LDS);
 // the results are the weights cnt - ceil(jsum / 6) (kmer_weight), jsum = the classes of the counted windows without a
 // read N (an absent window's class is 0 in the table).  Two more LDS lookups per base, for those ladders only.
-template <bool NCLS>
-__device__ __forceinline__ void kmer_counts(const uint32_t* rec, int L, const uint32_t* bm, const uint32_t* kc, int& cnt0, int& cnt1) {
+// TAIL: also the per-lane tail counts of the two strands (kmer_host.h), from the plain presence masks, for R rows per
+// lane: every word leaves one entry per strand in the thread's column of tl (LDS, TAIL_WORDS x 64 words per strand), the
+// 16 counts of a strand are taken from them after the loop and stored as one 16-byte vector -> tail[0 .. 31].
+constexpr int TAIL_WORDS = 10;   // words of a read of at most 160 bases: the instantiations that read the table
+template <bool NCLS, bool TAIL>
+__device__ __forceinline__ void kmer_counts(const uint32_t* rec, int L, const uint32_t* bm, const uint32_t* kc, int& cnt0, int& cnt1,
+                                            uint32_t* tl = nullptr, int R = 0, uint8_t* tail = nullptr) {
     const int nb = (L + 15) >> 4;
     uint32_t prev = 0, mprev = 0;
     cnt0 = cnt1 = 0;
@@ -1027,10 +1069,21 @@ __device__ __forceinline__ void kmer_counts(const uint32_t* rec, int L, const ui
                 j1 += use ? (int)__builtin_amdgcn_ubfe(kc[512 + at4], sh, 4) : 0;
             }
         }
+        if (TAIL) {
+            tl[wi * 64] = kmer_host::tail_entry((b0 | hn) & cm, cnt0);
+            tl[(TAIL_WORDS + wi) * 64] = kmer_host::tail_entry((b1 | hn) & cm, cnt1);
+        }
         cnt0 += __builtin_popcount((b0 | hn) & cm);
         cnt1 += __builtin_popcount((b1 | hn) & cm);
         prev = w;
         mprev = m;
+    }
+    if (TAIL) {
+        uint32_t t0[4], t1[4];
+        kmer_host::tail_pack(tl, 64, nb, cnt0, R, t0);
+        kmer_host::tail_pack(tl + TAIL_WORDS * 64, 64, nb, cnt1, R, t1);
+        reinterpret_cast<uint4*>(tail)[0] = make_uint4(t0[0], t0[1], t0[2], t0[3]);
+        reinterpret_cast<uint4*>(tail)[1] = make_uint4(t1[0], t1[1], t1[2], t1[3]);
     }
     if (NCLS) {
         cnt0 = kmer_weight(cnt0, j0);
@@ -1058,6 +1111,11 @@ __global__ __launch_bounds__(64) void read_class_kernel(SwArgs a, uint8_t* read_
     __shared__ uint32_t kc[2][512];   // the N classes of the 6-mers, for a ladder whose templates hold an N
     __shared__ int hist[UNIT_BINS];
     const bool ncls = filt && ld->kmer_n != 0;   // (per ladder: the same for the whole workgroup)
+    // The tail counts are read by the 7- and 10-row instantiations only (steady_exit's second tier); every other read's
+    // entries say "no bound", so that a reader needs no test of its own.
+    __shared__ uint32_t tl[2 * TAIL_WORDS * 64];
+    const int tail_R = a.max_rows / 16;
+    const bool tails = filt && (tail_R == 7 || tail_R == 10);
     if (filt) {
         for (int k = threadIdx.x; k < 256; k += (int)blockDim.x) bm[k >> 7][k & 127] = a.seqw[ld->kmer_off[k >> 7] + (k & 127)];
     }
@@ -1070,9 +1128,19 @@ __global__ __launch_bounds__(64) void read_class_kernel(SwArgs a, uint8_t* read_
         int cnt0 = CNT_UNFILTERED, cnt1 = CNT_UNFILTERED;
         const int L = a.read_len[rd];
         // over-long reads go to the SW kernel, which flags them (in pass A: unfiltered reads have bit 0)
+        uint8_t* const tail = a.read_tail + (int64_t)rd * (2 * kmer_host::TAIL_LANES);
         if (filt && L <= a.max_rows) {
-            if (ncls) kmer_counts<true>(a.packed + a.read_off[rd], L, &bm[0][0], &kc[0][0], cnt0, cnt1);
-            else kmer_counts<false>(a.packed + a.read_off[rd], L, &bm[0][0], nullptr, cnt0, cnt1);
+            if (tails) {
+                if (ncls) kmer_counts<true, true>(a.packed + a.read_off[rd], L, &bm[0][0], &kc[0][0], cnt0, cnt1, tl + threadIdx.x, tail_R, tail);
+                else kmer_counts<false, true>(a.packed + a.read_off[rd], L, &bm[0][0], nullptr, cnt0, cnt1, tl + threadIdx.x, tail_R, tail);
+            } else {
+                if (ncls) kmer_counts<true, false>(a.packed + a.read_off[rd], L, &bm[0][0], &kc[0][0], cnt0, cnt1);
+                else kmer_counts<false, false>(a.packed + a.read_off[rd], L, &bm[0][0], nullptr, cnt0, cnt1);
+            }
+        }
+        if (!(tails && L <= a.max_rows)) {
+            reinterpret_cast<uint4*>(tail)[0] = make_uint4(~0u, ~0u, ~0u, ~0u);
+            reinterpret_cast<uint4*>(tail)[1] = make_uint4(~0u, ~0u, ~0u, ~0u);
         }
         read_cnt[rd] = cnt0 | cnt1 << 16;
         a.best[rd] = -1;

@@ -56,6 +56,7 @@ struct SwArgs {
     unsigned long long* stats;  // [SW_STAT_SLOTS][8], slot = workgroup & (SW_STAT_SLOTS - 1): work counters: trunk cols, continuation-pass cols, templates combined/dropped/emitted-from-trunk, waves, read-columns, reads handed to pass B
     int32_t* best;              // per read: the arg-max word of sw_cont_kernel, carried from the strand-0 launch to the strand-1 launch
     const int32_t* read_cnt;    // per read: the 6-mer weights W0 | W1 << 16 of read_class_kernel (the score cap of a strand)
+    uint8_t* read_tail;         // per read: [2 strands][16 lanes] tail counts of read_class_kernel (kmer_host.h; 255 = no bound), read by steady_exit
 };
 
 // per-wave counter updates are spread over this many 64-byte lines: half a million waves adding to one line
